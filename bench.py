@@ -21,9 +21,13 @@ multi-GPU: one process per GPU, queries sharded, references replicated, the two 
                               score normalisation against a 2M-row noise set INSIDE the timed step
                               (vsc/baseline/sscd_baseline.py:193-204), 2M reference frames replicated.
 
-Prints ONE JSON line on rank 0 (see the driver contract in the task statement); adds
-"roofline" (the dominant kernel, measured live with HIP events on the engine's stream), "kernels"
-(every kernel class of a step: ms, achieved TFLOP/s or GB/s against its peak) and, at N=1,
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype and ms_per_step (milliseconds per timed
+step) of the headline.  A plain run does only that: set-up, --warmup steps, --steps timed steps, the line.
+`--dump-outputs DIR` then writes what the last timed step returned to its caller (candidate table, localised segments,
+final radius) as DIR/<name>.npy, float32 / float64, below 64 MB in all (a fixed, seeded sample of rows beyond that).
+`--full` adds "result_digest" (sha256 of that result), "roofline" (the dominant kernel, measured live with HIP events
+on the engine's stream during the timed steps), "kernels" (every kernel class of a step: ms, achieved TFLOP/s or GB/s
+against its peak), at N > 1 "sharded_search" and a cross-rank check of the candidate tables, and at N=1
 "extra" (untimed legs after the headline measurement: BASELINE configs[1]'s shape -- 8000 query videos x 2M reference
 frames without score normalisation, a few steps --, its 200k x 2M k-NN as written, query-set upload, score
 normalisation of 200k rows, one search on the all-fp32 route) and
@@ -57,8 +61,13 @@ def parse():
     ap.add_argument("--ref-videos", type=int, default=40000)
     ap.add_argument("--ref-frames", type=int, default=50)
     ap.add_argument("--dim", type=int, default=512)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the untimed k-NN / score-norm / all-fp32 legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also report the result digest, per-kernel / roofline figures, the untimed extra legs and the "
+                         "CPU baseline (a plain run prints the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, < 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the untimed k-NN / score-norm / all-fp32 legs")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--scaling", choices=("weak", "strong"), default="strong",
                     help="weak: --query-videos per GPU (configs[1] shape); strong: --total-query-videos split over the "
@@ -158,6 +167,38 @@ def result_digest(torch, matcher, res):
         out[k] = hashlib.sha256(v).hexdigest()[:16]
     return {"result_digest": whole.hexdigest()[:32], "parts": out, "n_boxes": int(boxes.shape[0]),
             "tie_on_cut": bool(res.tie_on_cut), "ties_dropped": bool(res.ties_dropped)}
+
+
+DUMP_BYTES = 60_000_000  # --dump-outputs: payload bound, so that the files stay below 64 MB with their headers
+
+
+def output_arrays(torch, matcher, res):
+    """What a caller of the timed path receives from its last step, as float64 (integers, exact below 2**53) and float32
+    (scores) arrays: the candidate table (query video, reference video, score), the localised segments (index into the
+    candidate table, q_lo, r_lo, q_hi, r_hi, MaxSim - bias) in the single-process order, and the final radius.  The
+    segment table is gathered over the ranks (a collective at N > 1: every rank calls this)."""
+    boxes = matcher.gather_boxes(res)
+    return {
+        "radius": np.array([res.radius], dtype=np.float32),
+        "cand_query": res.cand_q.cpu().numpy().astype(np.float64),
+        "cand_ref": res.cand_r.cpu().numpy().astype(np.float64),
+        "cand_score": res.cand_score.cpu().numpy().astype(np.float32),
+        "box_cand": boxes[:, 0].cpu().numpy().astype(np.float64),
+        "box_coords": boxes[:, 1:5].cpu().numpy().astype(np.float64),
+        "box_score": boxes[:, 5].to(torch.int32).cpu().numpy().view(np.float32),
+    }
+
+
+def dump_outputs(path, arrays):
+    """DIR/<name>.npy for every array.  Above DUMP_BYTES in all, every array keeps the same share of its rows, a fixed
+    seeded sample (arrays of one length keep the same rows, so the tables stay aligned)."""
+    os.makedirs(path, exist_ok=True)
+    frac = min(1.0, DUMP_BYTES / max(1, sum(a.nbytes for a in arrays.values())))
+    for name, a in arrays.items():
+        if frac < 1.0 and a.shape[0] > 1:
+            keep = np.random.default_rng(0).choice(a.shape[0], max(1, int(a.shape[0] * frac)), replace=False)
+            a = a[np.sort(keep)]
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a))
 
 
 def host_cores() -> int:
@@ -738,32 +779,41 @@ def main():
 
     for _ in range(args.warmup):
         res = step()
-    matcher.index.profile(True)
-    matcher.index.profile_read(reset=True)
-    if norm is not None:
-        norm.noise_index.profile(True)
-        norm.noise_index.profile_read(reset=True)
-    _lib.check(_lib.lib().vsc_aux_profile(1))
-    _aux(0), _aux(1)
+    if args.full:
+        # per-kernel accounting (HIP events on the engine's stream) over the timed steps: --full only
+        matcher.index.profile(True)
+        matcher.index.profile_read(reset=True)
+        if norm is not None:
+            norm.noise_index.profile(True)
+            norm.noise_index.profile_read(reset=True)
+        _lib.check(_lib.lib().vsc_aux_profile(1))
+        _aux(0), _aux(1)
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         res = step()
     barrier()
     dt = time.perf_counter() - t0
-    prof = matcher.index.profile_read(reset=True)
-    nprof = norm.noise_index.profile_read(reset=True) if norm is not None else None
-    pm_ms, pm_calls, pm_bytes = _aux(0)
-    tn_ms, tn_calls, tn_bytes = _aux(1)
-    digest = result_digest(torch, matcher, res)   # (collective at N > 1: every rank takes part, all hold the same tables)
-    # the sharded search's phases of the LAST step, max over ranks (dist.PhaseTimer: recorded without synchronising)
-    shard_phases = None
-    if world > 1 and getattr(matcher, "last_shard_stats", None):
-        shard_phases = vdist.reduce_phase_report(matcher.last_shard_stats.get("phases", {}), dev)
     if use_dist:
         t = torch.tensor([dt], dtype=torch.float64, device="cpu" if share_gpu else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs:
+        arrays = output_arrays(torch, matcher, res)   # (collective at N > 1: every rank takes part)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, arrays)
+        del arrays
+    if args.full:
+        prof = matcher.index.profile_read(reset=True)
+        nprof = norm.noise_index.profile_read(reset=True) if norm is not None else None
+        pm_ms, pm_calls, pm_bytes = _aux(0)
+        tn_ms, tn_calls, tn_bytes = _aux(1)
+        digest = result_digest(torch, matcher, res)   # (collective at N > 1: every rank takes part, all hold the same tables)
+        # the sharded search's phases of the LAST step, max over ranks (dist.PhaseTimer: recorded without synchronising)
+        shard_phases = None
+        if world > 1 and getattr(matcher, "last_shard_stats", None):
+            shard_phases = vdist.reduce_phase_report(matcher.last_shard_stats.get("phases", {}), dev)
+    if use_dist and args.full:
         # every rank must hold the same global candidate table (the sharded merge is deterministic)
         h = torch.stack([res.cand_q.to(torch.int64).sum(), res.cand_r.to(torch.int64).sum(),
                          res.cand_score.contiguous().view(torch.int32).to(torch.int64).sum()])
@@ -776,96 +826,6 @@ def main():
             dist.all_gather(hs, h)
         assert all(torch.equal(x, hs[0]) for x in hs), "candidate tables differ between ranks"
     if rank == 0:
-        steps = args.steps
-        # Dominant kernel = the similarity kernel class with the most time on the engine's stream: the int8 panel
-        # pre-filter (csrc/sim_i8p.hip), the fp16 one (csrc/sim_f16p.hip) or the exact fp32 kernel.  achieved =
-        # algorithmic operations (2 * rows * refs * dim of its launches) / their HIP-event time.
-        classes = {
-            "i8": ("sim_i8p_kernel (panel-stationary int8 MFMA pre-filter on v_mfma_i32_16x16x64_i8: the kernel's own launches "
-                   "-- the sparse batches of the search and the 1-NN passes of the score normalisation; the quantisation / "
-                   "sorting of its query rows is reported under kernels as its preamble)", INT8_MFMA_PEAK_TOPS, "TOP/s"),
-            "f16": ("sim_f16p_kernel (panel-stationary fp16 MFMA pre-filter; exact fp32 re-scoring of its candidates "
-                    "follows)", FP16_MFMA_PEAK_TFLOPS, "TFLOP/s"),
-            "sim": ("sim_thresh_kernel (fp32 MFMA similarity + fused threshold compaction)", FP32_MFMA_PEAK_TFLOPS, "TFLOP/s"),
-        }
-        # (configs[3]: the search index and the noise index of the score normalisation launch the same kernels)
-        both = dict(prof)
-        if nprof is not None:
-            for c in classes:
-                for f in ("ms", "flops", "launches"):
-                    both[f"{c}_{f}"] = prof.get(f"{c}_{f}", 0) + nprof.get(f"{c}_{f}", 0)
-        dom = max(classes, key=lambda c: both.get(f"{c}_ms", 0.0))
-        k_ms, k_flops, k_launches = both[f"{dom}_ms"], both[f"{dom}_flops"], both[f"{dom}_launches"]
-        peak = classes[dom][1]
-        achieved = (k_flops / 1e12) / (k_ms / 1e3) if k_ms > 0 else 0.0
-        # HBM-side bytes per launch of the dominant kernel come from the committed PMC passes of the SAME kernel
-        # (FETCH_SIZE / WRITE_SIZE cannot be sampled from inside the process): the newest profiles/r*_roofline.json names
-        # the kernel, the commit it was measured at, the rocprofv3 files and the hash of the kernel's source file then --
-        # compared with the file as it is now, so the line says whether the figure belongs to this very kernel
-        traffic, traffic_src = None, None
-        try:
-            import glob
-            import hashlib
-            rpath = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_roofline.json")))[-1]
-            with open(rpath) as fh:
-                rj = json.load(fh)
-            if rj.get("kernel_class") == dom:
-                traffic = float(rj["hbm_bytes_per_launch"])
-                traffic_src = f"profiles/{os.path.basename(rpath)}, measured at commit {rj.get('commit', '?')}"
-                if rj.get("kernel_source"):
-                    with open(os.path.join(ROOT, rj["kernel_source"]), "rb") as fh:
-                        same = hashlib.sha256(fh.read()).hexdigest()[:16] == rj.get("kernel_source_sha256_16")
-                    traffic_src += f"; {rj['kernel_source']} {'unchanged' if same else 'CHANGED'} since"
-        except Exception:
-            pass
-        dpad_bytes = 8 * ((dim + 63) // 64 * 64)  # two packed fp32 rows per re-scored candidate
-        cand = prof.get("candidates", 0)
-        kernels = {
-            "sim_i8p_kernel (int8 MFMA pre-filter, sparse batches)": {
-                "ms_per_step": prof.get("i8_ms", 0.0) / steps, "launches_per_step": prof.get("i8_launches", 0) / steps,
-                "achieved": _rate(prof.get("i8_flops", 0.0), prof.get("i8_ms", 0.0), 1e12),
-                "peak": INT8_MFMA_PEAK_TOPS, "unit": "TOP/s", "bound": "mfma"},
-            "int8 launches' preamble (row thresholds / scales, sort of the launch's rows, quantisation of the panels)": {
-                "ms_per_step": prof.get("i8_prep_ms", 0.0) / steps, "launches_per_step": prof.get("i8_prep_launches", 0) / steps},
-            "sim_f16p_kernel (fp16 MFMA pre-filter)": {
-                "ms_per_step": prof.get("f16_ms", 0.0) / steps, "launches_per_step": prof.get("f16_launches", 0) / steps,
-                "achieved": _rate(prof.get("f16_flops", 0.0), prof.get("f16_ms", 0.0), 1e12),
-                "peak": FP16_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "bound": "mfma"},
-            "sim_thresh_kernel (exact fp32 MFMA, dense early batches)": {
-                "ms_per_step": prof["sim_ms"] / steps, "achieved": _rate(prof["sim_flops"], prof["sim_ms"], 1e12),
-                "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "bound": "mfma"},
-            "rescore_kernel (exact fp32 chain of the candidates)": {
-                "ms_per_step": prof.get("rescore_ms", 0.0) / steps,
-                # HBM/fabric side: one REFERENCE row per candidate (a random 2 KB read of the 4 GB image; the query rows
-                # of a segment are one 128-row panel and stay in L2).  l2_to_cu counts both rows.
-                "achieved": _rate(float(cand) * (dpad_bytes // 2) * steps, prof.get("rescore_ms", 0.0), 1e9),
-                "l2_to_cu_GBs": _rate(float(cand) * dpad_bytes * steps, prof.get("rescore_ms", 0.0), 1e9),
-                "peak": HBM_PEAK_GBS, "unit": "GB/s", "bound": "hbm / fabric gather",
-                "note": f"{cand} candidates of the last search x {dpad_bytes // 2} B reference row (+ as many query-row bytes from L2)"},
-            "select_* (radix select + compaction of the re-thresholds)": {
-                "ms_per_step": prof.get("select_ms", 0.0) / steps, "launch_groups_per_step": prof.get("select_launches", 0) / steps},
-            "final ordering of the kept hits (radix sorts)": {
-                "ms_per_step": prof.get("sort_ms", 0.0) / steps,
-                "achieved": _rate(prof.get("sort_flops", 0.0), prof.get("sort_ms", 0.0), 1e9), "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "bound": "hbm", "note": "algorithmic bytes = 12 B per kept hit in; ~20 passes inside"},
-            "pair_max (sort by pair + segmented max + rank sort)": {
-                "ms_per_step": pm_ms / steps, "achieved": _rate(pm_bytes, pm_ms, 1e9), "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "bound": "hbm"},
-            "tn_pair_kernel (Temporal Network, one pair per wavefront)": {
-                "ms_per_step": tn_ms / steps, "achieved": _rate(tn_bytes, tn_ms, 1e9), "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "bound": "hbm by its bytes (instruction-issue-bound in practice: DESIGN.md 8.6)",
-                "note": "algorithmic bytes = 4 * dim * (Lq + Lr) per pair + boxes"},
-        }
-        if nprof is not None:
-            kernels["score normalisation of the query set (1-NN vs the noise index: exact subset pass + pre-filter + re-scoring)"] = {
-                "ms_per_step": (nprof["sim_ms"] + nprof["f16_ms"] + nprof["i8_ms"] + nprof.get("i8_prep_ms", 0.0) + nprof["rescore_ms"]) / steps,
-                "int8_prefilter_ms_per_step": nprof["i8_ms"] / steps, "int8_preamble_ms_per_step": nprof.get("i8_prep_ms", 0.0) / steps,
-                "fp16_prefilter_ms_per_step": nprof["f16_ms"] / steps,
-                "achieved": _rate(nprof["i8_flops"] + nprof["f16_flops"], nprof["i8_ms"] + nprof["f16_ms"], 1e12),
-                "unit": "T(FL)OP/s of the pre-filter passes"}
-        for v in kernels.values():
-            if "achieved" in v and v.get("peak"):
-                v["frac"] = v["achieved"] / v["peak"]
         total_videos = n_qv_total * args.steps
         if strong:
             workload = (f"BASELINE configs[3]: full pipeline incl. score normalisation + TN localisation, {n_qv_total} query "
@@ -888,11 +848,6 @@ def main():
             "dtype_note": "every reported score is the exact fp32 fma chain (bit-identical to the all-fp32 "
                           "path); int8 and fp16 MFMA only pre-filter pairs, each with a rigorous error bound",
             "data": "synthetic" if args.data == "gaussian" else f"synthetic ({args.data})",
-            "result_digest": digest["result_digest"],
-            "result_digest_parts": dict(digest["parts"], n_boxes=digest["n_boxes"], tie_on_cut=digest["tie_on_cut"],
-                                        ties_dropped=digest["ties_dropped"],
-                                        note="sha256 of (final radius | candidate table | localised segments): identical for "
-                                             "--gpus 1 and --gpus N runs of the same command line"),
             "process_group": pg,
             "config": {
                 "workload": workload,
@@ -902,22 +857,120 @@ def main():
                 "score_normalisation_in_step": strong,
                 "parallelism": f"query-sharded x{world}" if world > 1 else "single GPU",
             },
-            "roofline": {
-                "kernel": classes[dom][0],
-                "bound": "mfma",
-                "achieved": achieved,
-                "peak": peak,
-                "unit": classes[dom][2],
-                "frac": achieved / peak,
-                "traffic": traffic,
-                "traffic_unit": f"bytes/launch (PMC FETCH_SIZE x2 + WRITE_SIZE; {traffic_src})" if traffic else None,
-                "launches": k_launches,
-                "kernel_ms_per_step": k_ms / args.steps,
-                "prefilter_candidates_last_search": cand,
-            },
-            "kernels": kernels,
         }
-        if world > 1:
+        if args.full:
+            steps = args.steps
+            # Dominant kernel = the similarity kernel class with the most time on the engine's stream: the int8 panel
+            # pre-filter (csrc/sim_i8p.hip), the fp16 one (csrc/sim_f16p.hip) or the exact fp32 kernel.  achieved =
+            # algorithmic operations (2 * rows * refs * dim of its launches) / their HIP-event time.
+            classes = {
+                "i8": ("sim_i8p_kernel (panel-stationary int8 MFMA pre-filter on v_mfma_i32_16x16x64_i8: the kernel's own launches "
+                       "-- the sparse batches of the search and the 1-NN passes of the score normalisation; the quantisation / "
+                       "sorting of its query rows is reported under kernels as its preamble)", INT8_MFMA_PEAK_TOPS, "TOP/s"),
+                "f16": ("sim_f16p_kernel (panel-stationary fp16 MFMA pre-filter; exact fp32 re-scoring of its candidates "
+                        "follows)", FP16_MFMA_PEAK_TFLOPS, "TFLOP/s"),
+                "sim": ("sim_thresh_kernel (fp32 MFMA similarity + fused threshold compaction)", FP32_MFMA_PEAK_TFLOPS, "TFLOP/s"),
+            }
+            # (configs[3]: the search index and the noise index of the score normalisation launch the same kernels)
+            both = dict(prof)
+            if nprof is not None:
+                for c in classes:
+                    for f in ("ms", "flops", "launches"):
+                        both[f"{c}_{f}"] = prof.get(f"{c}_{f}", 0) + nprof.get(f"{c}_{f}", 0)
+            dom = max(classes, key=lambda c: both.get(f"{c}_ms", 0.0))
+            k_ms, k_flops, k_launches = both[f"{dom}_ms"], both[f"{dom}_flops"], both[f"{dom}_launches"]
+            peak = classes[dom][1]
+            achieved = (k_flops / 1e12) / (k_ms / 1e3) if k_ms > 0 else 0.0
+            # HBM-side bytes per launch of the dominant kernel come from the committed PMC passes of the SAME kernel
+            # (FETCH_SIZE / WRITE_SIZE cannot be sampled from inside the process): the newest profiles/r*_roofline.json names
+            # the kernel, the commit it was measured at, the rocprofv3 files and the hash of the kernel's source file then --
+            # compared with the file as it is now, so the line says whether the figure belongs to this very kernel
+            traffic, traffic_src = None, None
+            try:
+                import glob
+                import hashlib
+                rpath = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_roofline.json")))[-1]
+                with open(rpath) as fh:
+                    rj = json.load(fh)
+                if rj.get("kernel_class") == dom:
+                    traffic = float(rj["hbm_bytes_per_launch"])
+                    traffic_src = f"profiles/{os.path.basename(rpath)}, measured at commit {rj.get('commit', '?')}"
+                    if rj.get("kernel_source"):
+                        with open(os.path.join(ROOT, rj["kernel_source"]), "rb") as fh:
+                            same = hashlib.sha256(fh.read()).hexdigest()[:16] == rj.get("kernel_source_sha256_16")
+                        traffic_src += f"; {rj['kernel_source']} {'unchanged' if same else 'CHANGED'} since"
+            except Exception:
+                pass
+            dpad_bytes = 8 * ((dim + 63) // 64 * 64)  # two packed fp32 rows per re-scored candidate
+            cand = prof.get("candidates", 0)
+            kernels = {
+                "sim_i8p_kernel (int8 MFMA pre-filter, sparse batches)": {
+                    "ms_per_step": prof.get("i8_ms", 0.0) / steps, "launches_per_step": prof.get("i8_launches", 0) / steps,
+                    "achieved": _rate(prof.get("i8_flops", 0.0), prof.get("i8_ms", 0.0), 1e12),
+                    "peak": INT8_MFMA_PEAK_TOPS, "unit": "TOP/s", "bound": "mfma"},
+                "int8 launches' preamble (row thresholds / scales, sort of the launch's rows, quantisation of the panels)": {
+                    "ms_per_step": prof.get("i8_prep_ms", 0.0) / steps, "launches_per_step": prof.get("i8_prep_launches", 0) / steps},
+                "sim_f16p_kernel (fp16 MFMA pre-filter)": {
+                    "ms_per_step": prof.get("f16_ms", 0.0) / steps, "launches_per_step": prof.get("f16_launches", 0) / steps,
+                    "achieved": _rate(prof.get("f16_flops", 0.0), prof.get("f16_ms", 0.0), 1e12),
+                    "peak": FP16_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "bound": "mfma"},
+                "sim_thresh_kernel (exact fp32 MFMA, dense early batches)": {
+                    "ms_per_step": prof["sim_ms"] / steps, "achieved": _rate(prof["sim_flops"], prof["sim_ms"], 1e12),
+                    "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "bound": "mfma"},
+                "rescore_kernel (exact fp32 chain of the candidates)": {
+                    "ms_per_step": prof.get("rescore_ms", 0.0) / steps,
+                    # HBM/fabric side: one REFERENCE row per candidate (a random 2 KB read of the 4 GB image; the query rows
+                    # of a segment are one 128-row panel and stay in L2).  l2_to_cu counts both rows.
+                    "achieved": _rate(float(cand) * (dpad_bytes // 2) * steps, prof.get("rescore_ms", 0.0), 1e9),
+                    "l2_to_cu_GBs": _rate(float(cand) * dpad_bytes * steps, prof.get("rescore_ms", 0.0), 1e9),
+                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "bound": "hbm / fabric gather",
+                    "note": f"{cand} candidates of the last search x {dpad_bytes // 2} B reference row (+ as many query-row bytes from L2)"},
+                "select_* (radix select + compaction of the re-thresholds)": {
+                    "ms_per_step": prof.get("select_ms", 0.0) / steps, "launch_groups_per_step": prof.get("select_launches", 0) / steps},
+                "final ordering of the kept hits (radix sorts)": {
+                    "ms_per_step": prof.get("sort_ms", 0.0) / steps,
+                    "achieved": _rate(prof.get("sort_flops", 0.0), prof.get("sort_ms", 0.0), 1e9), "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "bound": "hbm", "note": "algorithmic bytes = 12 B per kept hit in; ~20 passes inside"},
+                "pair_max (sort by pair + segmented max + rank sort)": {
+                    "ms_per_step": pm_ms / steps, "achieved": _rate(pm_bytes, pm_ms, 1e9), "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "bound": "hbm"},
+                "tn_pair_kernel (Temporal Network, one pair per wavefront)": {
+                    "ms_per_step": tn_ms / steps, "achieved": _rate(tn_bytes, tn_ms, 1e9), "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "bound": "hbm by its bytes (instruction-issue-bound in practice: DESIGN.md 8.6)",
+                    "note": "algorithmic bytes = 4 * dim * (Lq + Lr) per pair + boxes"},
+            }
+            if nprof is not None:
+                kernels["score normalisation of the query set (1-NN vs the noise index: exact subset pass + pre-filter + re-scoring)"] = {
+                    "ms_per_step": (nprof["sim_ms"] + nprof["f16_ms"] + nprof["i8_ms"] + nprof.get("i8_prep_ms", 0.0) + nprof["rescore_ms"]) / steps,
+                    "int8_prefilter_ms_per_step": nprof["i8_ms"] / steps, "int8_preamble_ms_per_step": nprof.get("i8_prep_ms", 0.0) / steps,
+                    "fp16_prefilter_ms_per_step": nprof["f16_ms"] / steps,
+                    "achieved": _rate(nprof["i8_flops"] + nprof["f16_flops"], nprof["i8_ms"] + nprof["f16_ms"], 1e12),
+                    "unit": "T(FL)OP/s of the pre-filter passes"}
+            for v in kernels.values():
+                if "achieved" in v and v.get("peak"):
+                    v["frac"] = v["achieved"] / v["peak"]
+            out.update({
+                "result_digest": digest["result_digest"],
+                "result_digest_parts": dict(digest["parts"], n_boxes=digest["n_boxes"], tie_on_cut=digest["tie_on_cut"],
+                                            ties_dropped=digest["ties_dropped"],
+                                            note="sha256 of (final radius | candidate table | localised segments): identical for "
+                                                 "--gpus 1 and --gpus N runs of the same command line"),
+                "roofline": {
+                    "kernel": classes[dom][0],
+                    "bound": "mfma",
+                    "achieved": achieved,
+                    "peak": peak,
+                    "unit": classes[dom][2],
+                    "frac": achieved / peak,
+                    "traffic": traffic,
+                    "traffic_unit": f"bytes/launch (PMC FETCH_SIZE x2 + WRITE_SIZE; {traffic_src})" if traffic else None,
+                    "launches": k_launches,
+                    "kernel_ms_per_step": k_ms / args.steps,
+                    "prefilter_candidates_last_search": cand,
+                },
+                "kernels": kernels,
+            })
+        if world > 1 and args.full:
             # what the sharded search did in the last step on rank 0 (engine.DeviceMatcher.sharded_schedule_search): batches
             # searched, and -- with VSC_SHARD_DEBUG=1, which synchronises around every phase -- the seconds per phase.  In the
             # share-GPU debugging set-up t_gather / t_handover are host-staged gloo transfers and the GPU phases are the work
@@ -934,7 +987,7 @@ def main():
                     "batch (library calls); count = per-batch all-reduce of the kept total (+ its host sync); events = exact "
                     "distributed (K+1)-th best by radix-select histograms + filter; handover = all-to-all of the kept hits to "
                     "the row owners; final_sort_and_cut = radix sort + distributed cut at K")
-        if world == 1:
+        if world == 1 and args.full:
             # the untimed legs must never cost the headline line: a failure in one of them is reported, not raised
             if not args.no_extra:
                 try:

@@ -6,7 +6,7 @@ set -u
 tag=$1; shift
 out=$PWD/gpurun_out/$tag; mkdir -p $out
 export TMPDIR=/tmp
-cmd="python $PWD/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-extra $*"
+cmd="python $PWD/bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --no-extra $*"
 d=/tmp/kt_$tag; rm -rf $d
 (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d $d -o r -- $cmd > $out/trace.log 2>&1)
 db=$(find $d -name "*.db" | head -1)

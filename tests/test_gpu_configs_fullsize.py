@@ -203,7 +203,7 @@ def test_bench_default_line_under_torchrun_nproc1(gpu):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
            "--master-port", str(29600 + os.getpid() % 300), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1",
-           "--warmup", "1", "--no-extra", "--no-cpu-baseline"]
+           "--warmup", "1", "--full", "--no-extra", "--no-cpu-baseline"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{"metric"')]
@@ -214,3 +214,41 @@ def test_bench_default_line_under_torchrun_nproc1(gpu):
     assert rep["config"]["score_normalisation_in_step"] is True and "configs[3]" in rep["config"]["workload"]
     assert rep["config"]["hits"] == 48000000 and rep["config"]["candidates"] == 1000000 and rep["config"]["pairs_localized"] == 200000
     assert rep["value"] > 0 and 0.0 < rep["roofline"]["frac"] < 1.0
+
+
+def test_bench_plain_line_and_dumped_outputs(gpu, tmp_path):
+    """A plain `bench.py` run prints the headline alone; `--dump-outputs` writes what the last timed step returned, the
+    same arrays run after run, and they hash to the `result_digest` of a `--full` run of the same command line."""
+    import hashlib
+
+    small = ["--total-query-videos", "200", "--query-frames", "12", "--ref-videos", "300", "--ref-frames", "20",
+             "--noise-rows", "12000", "--steps", "2", "--warmup", "1"]
+
+    def run(dump_dir, *extra):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *small, "--dump-outputs", str(dump_dir), *extra],
+                             cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{"metric"')]
+        assert len(lines) == 1, out.stdout[-2000:]
+        arrays = {f[:-4]: np.load(os.path.join(dump_dir, f)) for f in sorted(os.listdir(dump_dir))}
+        return json.loads(lines[0]), arrays
+
+    plain, a = run(tmp_path / "plain")
+    full, b = run(tmp_path / "full", "--full", "--no-extra", "--no-cpu-baseline")
+    assert plain["steps"] == 2 and plain["ms_per_step"] > 0 and plain["value"] > 0
+    for key in ("unit", "higher_is_better", "dtype"):
+        assert key in plain
+    for key in ("result_digest", "roofline", "kernels", "extra", "cpu_baseline"):
+        assert key not in plain, key
+    assert "result_digest" in full and "roofline" in full
+    assert set(a) == {"radius", "cand_query", "cand_ref", "cand_score", "box_cand", "box_coords", "box_score"}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert len(a["cand_query"]) == plain["config"]["candidates"] and len(a["box_cand"]) == plain["config"]["matches"]
+    assert set(b) == set(a) and all(np.array_equal(a[k].view(np.uint8), b[k].view(np.uint8)) for k in a)
+    # the digest's byte layout (bench.result_digest): radius | candidate table | gathered segment table
+    boxes = np.concatenate([a["box_cand"][:, None], a["box_coords"],
+                            a["box_score"].view(np.int32).astype(np.float64)[:, None]], axis=1).astype(np.int64)
+    whole = hashlib.sha256(a["radius"].tobytes() + a["cand_query"].astype(np.int32).tobytes()
+                           + a["cand_ref"].astype(np.int32).tobytes() + a["cand_score"].view(np.int32).tobytes()
+                           + np.ascontiguousarray(boxes).tobytes())
+    assert whole.hexdigest()[:32] == full["result_digest"]

@@ -76,7 +76,9 @@ def build(force: bool = False) -> str:
         and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs)
     ):
         return LIB_PATH
-    subprocess.check_call(["make", "-C", CSRC, "-j", str(os.cpu_count() or 4)])
+    # at most 16 jobs: on a shared host os.cpu_count() is the whole machine, not this process's share of it
+    jobs = min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 4))
+    subprocess.check_call(["make", "-C", CSRC, "-j", str(jobs)])
     if os.environ.get("VSC_SKIP_LINT") != "1":
         # a fresh library is checked for the hazards the compiler cannot see inside the kernels' inline assembly
         # (scripts/lint_isa.py: VALU-written SGPRs read by VMEM too early, registers of outstanding stream loads touched
