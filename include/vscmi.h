@@ -48,6 +48,10 @@ extern "C" {
 #define VSC_METRIC_INNER_PRODUCT 0
 #define VSC_METRIC_L2 1
 
+/* how an index stores its reference rows (vsc/index.py:75-82: the codec_str handed to faiss.index_factory) */
+#define VSC_CODEC_FLAT 0   /* "Flat": fp32 rows */
+#define VSC_CODEC_SQFP16 1 /* "SQfp16" (faiss IndexScalarQuantizer, QT_fp16): IEEE half floats, scored in fp32 */
+
 #define VSC_TN_MAX_BOXES 16
 
 typedef struct vsc_index vsc_index_t;
@@ -115,6 +119,24 @@ int vsc_device_count(void);
  * Process-wide (first use): VSC_SIM_GRID (persistent grid of the exact similarity kernel), VSC_POISON_ALLOC=1
  * (fresh device buffers filled with 0xFF). */
 int vsc_index_create(int dim, int metric, int device, vsc_index_t** out);
+/* The same with a codec, fixed for the life of the handle; vsc_index_create means VSC_CODEC_FLAT.
+ *
+ * VSC_CODEC_SQFP16.  By definition the index on rows X behaves as the Flat index on
+ *     dec(X) = the rows rounded to IEEE half floats (round to nearest even, subnormals kept) and converted back:
+ * every search returns the rows, references and score BITS of that Flat index -- same routes, same options, same
+ * arithmetic contract (the fp32 chain over the query's fp32 values and the references' decoded values).  Rows that
+ * are already half floats (descriptor files written with --store_fp16) decode to themselves: the codec loses nothing
+ * on them.  The rows live once in HBM, as half floats in the layout the fp16 pre-filter reads; the packed fp32 image
+ * of a Flat handle is never allocated (512-d inner product: 1556 instead of 3604 bytes per row with both pre-filter
+ * images).  The store is kept whatever "prefilter" and the metric say; the int8 image, the excluded coordinates and
+ * the centre are derived from the decoded values.  The exact stage of the pre-filtered routes gathers its reference
+ * rows from the store; the exact kernels that stream whole rows (pre-filter off, exact k-NN subsets) run over
+ * bounded ranges of rows decoded into a scratch buffer.
+ * A row holding NaN, +-inf or a value beyond +-65504 makes vsc_index_add / _add_f16 fail with VSC_ERR_INVALID and
+ * leaves the index as it was.
+ * Read-only options of both codecs: "codec", and "ref_bytes" = bytes currently allocated for reference images of all
+ * kinds (store, pre-filter images, per-row tables). */
+int vsc_index_create_codec(int dim, int metric, int device, int codec, vsc_index_t** out);
 int vsc_index_destroy(vsc_index_t* idx);
 /* Programmatic form of the switches above (the reference's analogue: faiss.ParameterSpace().set_index_parameter(index,
  * name, value) on the object vsc/index.py:82 creates).  Options that decide which images of the reference rows are kept
@@ -133,6 +155,13 @@ int vsc_index_get_option(const vsc_index_t* idx, const char* name, double* value
  * library does NOT touch that stream again -- it may already be destroyed -- and drains the device instead. */
 int vsc_index_set_stream(vsc_index_t* idx, void* hip_stream, int own);
 int vsc_index_add(vsc_index_t* idx, const float* x, int64_t n, int x_mem);
+/* Rows that are already IEEE half floats ([n][dim] uint16 bit patterns, host or device).  SQfp16 handle: they reach
+ * the store without an fp32 copy on the host and without a staging buffer of fp32 size.  Flat handle: the result of
+ * vsc_index_add of the upcast array. */
+int vsc_index_add_f16(vsc_index_t* idx, const uint16_t* x, int64_t n, int x_mem);
+/* fp32 [n][dim] of rows [i0, i0 + n) as the searches see them: the rows as added (Flat), dec of them (SQfp16).
+ * (faiss index.reconstruct_n) */
+int vsc_index_reconstruct(vsc_index_t* idx, int64_t i0, int64_t n, float* out, int out_mem);
 int64_t vsc_index_ntotal(const vsc_index_t* idx);
 int vsc_index_dim(const vsc_index_t* idx);
 int vsc_index_metric(const vsc_index_t* idx);

@@ -29,12 +29,16 @@ MEM_HOST = 0
 MEM_DEVICE = 1
 METRIC_INNER_PRODUCT = 0
 METRIC_L2 = 1
+CODEC_FLAT = 0
+CODEC_SQFP16 = 1
+# the codec strings of VideoIndex / faiss.index_factory that exist here
+CODECS = {"Flat": CODEC_FLAT, "SQfp16": CODEC_SQFP16}
 TN_MAX_BOXES = 16
 
 # every symbol include/vscmi.h declares
 EXPORTS = (
     "vsc_last_error", "vsc_version", "vsc_device_count",
-    "vsc_index_create", "vsc_index_destroy", "vsc_index_add", "vsc_index_ntotal", "vsc_index_dim",
+    "vsc_index_create", "vsc_index_create_codec", "vsc_index_destroy", "vsc_index_add", "vsc_index_add_f16", "vsc_index_reconstruct", "vsc_index_ntotal", "vsc_index_dim",
     "vsc_index_metric", "vsc_index_set_hit_capacity", "vsc_index_sync", "vsc_index_knn",
     "vsc_index_set_option", "vsc_index_get_option", "vsc_index_set_stream", "vsc_tn_set_stream", "vsc_set_aux_stream",
     "vsc_index_range_search", "vsc_index_global_topk", "vsc_index_global_topk_seeded", "vsc_index_candidates", "vsc_pair_max", "vsc_sort_hits", "vsc_row_normalize",
@@ -146,7 +150,10 @@ def lib():
         L.vsc_version.restype = i32
         L.vsc_device_count.restype = i32
         L.vsc_index_create.argtypes = [i32, i32, i32, ctypes.POINTER(vp)]
+        L.vsc_index_create_codec.argtypes = [i32, i32, i32, i32, ctypes.POINTER(vp)]
         L.vsc_index_destroy.argtypes = [vp]
+        L.vsc_index_add_f16.argtypes = [vp, vp, i64, i32]
+        L.vsc_index_reconstruct.argtypes = [vp, i64, i64, vp, i32]
         L.vsc_index_add.argtypes = [vp, vp, i64, i32]
         L.vsc_index_ntotal.argtypes = [vp]
         L.vsc_index_ntotal.restype = i64
@@ -236,6 +243,17 @@ def ptr(a):
     # torch tensor (duck-typed: no torch import needed here)
     assert a.is_contiguous(), "tensor must be contiguous"
     return a.data_ptr(), (MEM_DEVICE if a.is_cuda else MEM_HOST)
+
+
+def codec_id(codec: str) -> int:
+    """VSC_CODEC_* of a codec string; NotImplementedError for the codecs this engine does not have."""
+    try:
+        return CODECS[codec]
+    except (KeyError, TypeError):
+        raise NotImplementedError(
+            f"codec {codec!r}: the MI355X engine implements the exhaustive index with the codecs "
+            f"{' and '.join(repr(c) for c in CODECS)} only"
+        ) from None
 
 
 def f32c(x):

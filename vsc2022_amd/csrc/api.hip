@@ -254,6 +254,9 @@ static int read_option(const vsc_index* idx, const char* name, double* out) {
     else if (is("i8_center_on")) *out = idx->i8_mu_on;        // (read-only: is the int8 reference image centred?)
     else if (is("i8_center_share")) *out = idx->i8_mu_ratio;  // (read-only: |mean|^2 / mean |row|^2 when it was decided)
     else if (is("i8_fallbacks")) *out = (double)idx->stat_i8_fallbacks;  // (read-only: searches that left int8 for fp16)
+    else if (is("codec")) *out = idx->codec;  // (read-only: VSC_CODEC_FLAT / VSC_CODEC_SQFP16, fixed at creation)
+    // (read-only: bytes allocated for reference images of all kinds -- store, pre-filter images, per-row tables)
+    else if (is("ref_bytes")) *out = (double)(idx->ref.bytes + idx->refh.bytes + idx->refn.bytes + idx->ref8.bytes + idx->ref8m.bytes);
     else {
         set_error("vsc_index_get_option: unknown option '%s'", name);
         return VSC_ERR_INVALID;
@@ -292,14 +295,20 @@ int vsc_device_count(void) {
 }
 
 int vsc_index_create(int dim, int metric, int device, vsc_index_t** out) {
-    if (!out || dim <= 0 || (metric != VSC_METRIC_INNER_PRODUCT && metric != VSC_METRIC_L2)) {
-        set_error("vsc_index_create: invalid argument (dim=%d metric=%d)", dim, metric);
+    return vsc_index_create_codec(dim, metric, device, VSC_CODEC_FLAT, out);
+}
+
+int vsc_index_create_codec(int dim, int metric, int device, int codec, vsc_index_t** out) {
+    if (!out || dim <= 0 || (metric != VSC_METRIC_INNER_PRODUCT && metric != VSC_METRIC_L2) ||
+        (codec != VSC_CODEC_FLAT && codec != VSC_CODEC_SQFP16)) {
+        set_error("vsc_index_create: invalid argument (dim=%d metric=%d codec=%d)", dim, metric, codec);
         return VSC_ERR_INVALID;
     }
     VSC_TRY(check_device(device));
     VSC_HIP(hipSetDevice(device));
     vsc_index* idx = new vsc_index();
     idx->dim = dim;
+    idx->codec = codec;
     idx->dpad = round_up(dim, K_PAD);
     idx->dpadh = round_up(dim, 128);
     idx->frag = idx->dpadh <= F16P_MAX_DPADH;
@@ -412,6 +421,18 @@ int vsc_index_sync(vsc_index_t* idx) {
 
 }  // extern "C"
 
+// SQfp16 codec: rows [r0, r0 + rows) of the store, decoded into ws.dec as packed fp32 and followed by 512 zero rows.
+// Rows of the store past the padded row count are not read (they come out as zeros).
+int decode_range(vsc_index* idx, int64_t r0, int64_t rows, float** out) {
+    const int64_t rows_out = round_up64(rows, ROW_PAD_REF) + ROW_PAD_REF;
+    VSC_TRY(idx->ws.dec.reserve((size_t)rows_out * idx->dpad * sizeof(float)));
+    VSC_TRY(launch_decode_rows(idx->refh.as<_Float16>(), idx->dpadh, idx->frag, r0, rows_out,
+                               std::min(r0 + rows, round_up64(idx->ntotal, ROW_PAD_REF)), idx->ws.dec.as<float>(), idx->dpad, true,
+                               idx->stream));
+    *out = idx->ws.dec.as<float>();
+    return VSC_OK;
+}
+
 // (Re)write rows [row0, row0 + rows) of the int8 image and their meta from the packed fp32 rows, with the index's
 // current set of excluded coordinates; the first `count_rows - row0` of them enter the looseness statistic.
 // The centre as the kernels read it: packed order, zero on the coordinates the image leaves out.
@@ -436,10 +457,25 @@ static int i8_decide_centre(vsc_index* idx, int64_t rows) {
     const int dpad = idx->dpad;
     VSC_TRY(idx->ws.tmp.reserve((size_t)2 * dpad * sizeof(double)));
     double* d_sum = idx->ws.tmp.as<double>();
-    VSC_TRY(launch_col_sums(idx->ref.as<float>(), rows, dpad, d_sum, d_sum + dpad, idx->stream));
     std::vector<double> h((size_t)2 * dpad);
+    if (sq16(idx)) {
+        // the decoded values, range by range; the ranges' sums are added up on the host
+        std::vector<double> part(h.size());
+        std::fill(h.begin(), h.end(), 0.0);
+        for (int64_t c0 = 0; c0 < rows; c0 += DEC_CHUNK_ROWS) {
+            const int64_t rc = std::min(DEC_CHUNK_ROWS, rows - c0);
+            float* dec = nullptr;
+            VSC_TRY(decode_range(idx, c0, rc, &dec));
+            VSC_TRY(launch_col_sums(dec, rc, dpad, d_sum, d_sum + dpad, idx->stream));
+            VSC_HIP(hipMemcpyAsync(part.data(), d_sum, part.size() * sizeof(double), hipMemcpyDeviceToHost, idx->stream));
+            VSC_HIP(hipStreamSynchronize(idx->stream));
+            for (size_t e = 0; e < h.size(); ++e) h[e] += part[e];
+        }
+    } else {
+    VSC_TRY(launch_col_sums(idx->ref.as<float>(), rows, dpad, d_sum, d_sum + dpad, idx->stream));
     VSC_HIP(hipMemcpyAsync(h.data(), d_sum, h.size() * sizeof(double), hipMemcpyDeviceToHost, idx->stream));
     VSC_HIP(hipStreamSynchronize(idx->stream));
+    }
     idx->i8_mu_host.assign((size_t)dpad, 0.0f);
     double mu2 = 0.0, e2 = 0.0;
     bool finite = true;
@@ -469,6 +505,16 @@ static int i8_quantise(vsc_index* idx, int64_t row0, int64_t rows, int64_t count
         for (int c = 0; same && c < idx->i8_ex.n; ++c) same = idx->i8_mu_ex.idx[c] == idx->i8_ex.idx[c];
         if (!same) VSC_TRY(i8_upload_centre(idx));
     }
+    if (sq16(idx)) {
+        // from the decoded values, range by range (the kernel indexes its source by absolute row)
+        for (int64_t c0 = row0; c0 < row0 + rows; c0 += DEC_CHUNK_ROWS) {
+            const int64_t rc = std::min(DEC_CHUNK_ROWS, row0 + rows - c0);
+            float* dec = nullptr;
+            VSC_TRY(decode_range(idx, c0, rc, &dec));
+            VSC_TRY(launch_quant_ref_frag(dec - c0 * idx->dpad, idx->dpad, idx->ref8.p, idx->ref8m.as<float4>(), c0, rc, idx->dpad8,
+                                          idx->i8_ex, idx->i8_mu_on ? idx->i8_mu.as<float>() : nullptr, idx->stream));
+        }
+    } else
     VSC_TRY(launch_quant_ref_frag(idx->ref.as<float>(), idx->dpad, idx->ref8.p, idx->ref8m.as<float4>(), row0, rows,
                                   idx->dpad8, idx->i8_ex, idx->i8_mu_on ? idx->i8_mu.as<float>() : nullptr, idx->stream));
     const int64_t real = std::max<int64_t>(0, std::min(row0 + rows, count_rows) - row0);
@@ -491,11 +537,31 @@ static int i8_after_add(vsc_index* idx, int64_t first_new, int64_t n, int64_t ne
     VSC_TRY(idx->ws.tmp.reserve((size_t)2 * dpad * sizeof(unsigned)));
     unsigned* d_mn = idx->ws.tmp.as<unsigned>();
     unsigned* d_mx = d_mn + dpad;
-    VSC_TRY(launch_dim_minmax(idx->ref.as<float>() + first_new * dpad, n, dpad, d_mn, d_mx, idx->stream));
     std::vector<unsigned> mn((size_t)dpad), mx((size_t)dpad);
+    if (sq16(idx)) {
+        // the decoded values, range by range; the ranges' keys are folded on the host
+        std::vector<unsigned> pmn((size_t)dpad), pmx((size_t)dpad);
+        std::fill(mn.begin(), mn.end(), 0xffffffffu);
+        std::fill(mx.begin(), mx.end(), 0u);
+        for (int64_t c0 = first_new; c0 < first_new + n; c0 += DEC_CHUNK_ROWS) {
+            const int64_t rc = std::min(DEC_CHUNK_ROWS, first_new + n - c0);
+            float* dec = nullptr;
+            VSC_TRY(decode_range(idx, c0, rc, &dec));
+            VSC_TRY(launch_dim_minmax(dec, rc, dpad, d_mn, d_mx, idx->stream));
+            VSC_HIP(hipMemcpyAsync(pmn.data(), d_mn, (size_t)dpad * sizeof(unsigned), hipMemcpyDeviceToHost, idx->stream));
+            VSC_HIP(hipMemcpyAsync(pmx.data(), d_mx, (size_t)dpad * sizeof(unsigned), hipMemcpyDeviceToHost, idx->stream));
+            VSC_HIP(hipStreamSynchronize(idx->stream));
+            for (int p = 0; p < dpad; ++p) {
+                mn[(size_t)p] = std::min(mn[(size_t)p], pmn[(size_t)p]);
+                mx[(size_t)p] = std::max(mx[(size_t)p], pmx[(size_t)p]);
+            }
+        }
+    } else {
+    VSC_TRY(launch_dim_minmax(idx->ref.as<float>() + first_new * dpad, n, dpad, d_mn, d_mx, idx->stream));
     VSC_HIP(hipMemcpyAsync(mn.data(), d_mn, (size_t)dpad * sizeof(unsigned), hipMemcpyDeviceToHost, idx->stream));
     VSC_HIP(hipMemcpyAsync(mx.data(), d_mx, (size_t)dpad * sizeof(unsigned), hipMemcpyDeviceToHost, idx->stream));
     VSC_HIP(hipStreamSynchronize(idx->stream));
+    }
     if (idx->cmin_key.empty()) {
         idx->cmin_key.assign((size_t)idx->dim, 0xffffffffu);
         idx->cmax_key.assign((size_t)idx->dim, 0u);
@@ -534,9 +600,69 @@ static int i8_after_add(vsc_index* idx, int64_t first_new, int64_t n, int64_t ne
     return i8_quantise(idx, first_new, need_rows - first_new, first_new + n);
 }
 
-extern "C" {
+// SQfp16 handle: rows [ntotal, ntotal + n) of the store from fp32 or fp16 rows (host sources staged in chunks of their
+// own element size: fp16 rows never exist as fp32 anywhere), rows up to `need_rows` zero filled.  A row fp16 cannot
+// hold fails the add: what was written is zero filled again, the index is as it was.
+static int store_rows(vsc_index* idx, const void* x, bool src16, int64_t n, int x_mem, int64_t need_rows) {
+    const size_t esz = src16 ? 2 : 4;
+    Workspace& ws = idx->ws;
+    VSC_TRY(ws.flag.reserve(16));
+    int* d_bad = ws.flag.as<int>();
+    VSC_HIP(hipMemsetAsync(d_bad, 0, sizeof(int), idx->stream));
+    _Float16* image = idx->refh.as<_Float16>();
+    float* norms = idx->refn.as<float>();
+    const int64_t first = idx->ntotal, rows_out = need_rows - first;
+    if (x_mem == VSC_MEM_DEVICE) {
+        VSC_TRY(launch_encode_rows(x, src16, n, idx->dim, image, norms + first, first, rows_out, idx->dpadh, idx->frag, d_bad, idx->stream));
+    } else {
+        const int64_t chunk_rows = std::max<int64_t>(1, (int64_t)(256ll << 20) / ((int64_t)idx->dim * (int64_t)esz));
+        VSC_TRY(ws.stage.reserve((size_t)std::min(chunk_rows, n) * idx->dim * esz));
+        for (int64_t r0 = 0; r0 < n; r0 += chunk_rows) {
+            const int64_t rows = std::min(chunk_rows, n - r0);
+            VSC_HIP(hipMemcpyAsync(ws.stage.p, static_cast<const char*>(x) + (size_t)r0 * idx->dim * esz, (size_t)rows * idx->dim * esz,
+                                   hipMemcpyHostToDevice, idx->stream));
+            const bool last = r0 + rows == n;
+            VSC_TRY(launch_encode_rows(ws.stage.p, src16, rows, idx->dim, image, norms + first + r0, first + r0,
+                                       last ? rows_out - r0 : rows, idx->dpadh, idx->frag, d_bad, idx->stream));
+            VSC_HIP(hipStreamSynchronize(idx->stream));  // staging buffer is reused
+        }
+    }
+    int bad = 0;
+    VSC_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, idx->stream));
+    VSC_HIP(hipStreamSynchronize(idx->stream));
+    if (bad) {
+        VSC_TRY(launch_encode_rows(nullptr, src16, 0, idx->dim, image, norms + first, first, rows_out, idx->dpadh, idx->frag, d_bad, idx->stream));
+        VSC_HIP(hipStreamSynchronize(idx->stream));
+        set_error("vsc_index_add: a row holds NaN, +-inf or a value beyond +-65504, which the SQfp16 codec cannot store; nothing was added");
+        return VSC_ERR_INVALID;
+    }
+    return VSC_OK;
+}
 
-int vsc_index_add(vsc_index_t* idx, const float* x, int64_t n, int x_mem) {
+// Flat handle, fp16 rows: decoded in bounded chunks (ws.dec) and packed like fp32 rows -- the result of `add` of the
+// upcast array.
+static int pack_f16_rows(vsc_index* idx, const uint16_t* x, int64_t n, int x_mem, float* dst, int64_t rows_out, const HalfImage& h) {
+    Workspace& ws = idx->ws;
+    const int64_t chunk_rows = std::max<int64_t>(1, (int64_t)(64ll << 20) / ((int64_t)idx->dim * 4));
+    VSC_TRY(ws.dec.reserve((size_t)std::min(chunk_rows, n) * idx->dim * 4));
+    if (x_mem != VSC_MEM_DEVICE) VSC_TRY(ws.stage.reserve((size_t)std::min(chunk_rows, n) * idx->dim * 2));
+    for (int64_t r0 = 0; r0 < n; r0 += chunk_rows) {
+        const int64_t rows = std::min(chunk_rows, n - r0);
+        const uint16_t* src = x + r0 * idx->dim;
+        if (x_mem != VSC_MEM_DEVICE) {
+            VSC_HIP(hipMemcpyAsync(ws.stage.p, src, (size_t)rows * idx->dim * 2, hipMemcpyHostToDevice, idx->stream));
+            src = ws.stage.as<uint16_t>();
+        }
+        VSC_TRY(launch_half_to_float(reinterpret_cast<const _Float16*>(src), rows * idx->dim, ws.dec.as<float>(), idx->stream));
+        const bool last = r0 + rows == n;
+        VSC_TRY(launch_pack_rows(ws.dec.as<float>(), rows, idx->dim, dst + r0 * idx->dpad, last ? rows_out - r0 : rows, idx->dpad, idx->stream));
+        if (h.rows) VSC_TRY(pack_half_any(ws.dec.as<float>(), rows, idx->dim, h, r0, last ? h.rows_out - r0 : rows, idx->stream));
+        VSC_HIP(hipStreamSynchronize(idx->stream));  // the buffers are reused
+    }
+    return VSC_OK;
+}
+
+static int index_add(vsc_index_t* idx, const void* x, bool src16, int64_t n, int x_mem) {
     if (!idx || n < 0 || (n > 0 && !x)) {
         set_error("vsc_index_add: invalid argument");
         return VSC_ERR_INVALID;
@@ -548,13 +674,14 @@ int vsc_index_add(vsc_index_t* idx, const float* x, int64_t n, int x_mem) {
     }
     VSC_HIP(hipSetDevice(idx->device));
     const int64_t need_rows = round_up64(idx->ntotal + n, ROW_PAD_REF);
+    const bool keep_half = idx->prefilter || sq16(idx);  // (SQfp16: the half image is the store)
     if (need_rows > idx->cap_rows) {
         // grow geometrically; keep the old rows
         int64_t cap = std::max<int64_t>(need_rows, idx->cap_rows + idx->cap_rows / 2);
         cap = round_up64(cap, ROW_PAD_REF);
         DevBuf nb, nh, nn, n8, n8m;
-        VSC_TRY(nb.reserve((size_t)cap * idx->dpad * 4));
-        if (idx->prefilter) {
+        if (!sq16(idx)) VSC_TRY(nb.reserve((size_t)cap * idx->dpad * 4));
+        if (keep_half) {
             // (+ one col-step of rows: a launch over the reference range [b, e) walks whole col-steps FROM b, and b is
             // only tile-aligned when the tests force the k-NN's levels on small indexes -- the per-row tables are read
             // with plain loads up to b + round_up(e - b, 512) <= cap + 511; the images go through bounds-checked
@@ -567,9 +694,10 @@ int vsc_index_add(vsc_index_t* idx, const float* x, int64_t n, int x_mem) {
             VSC_TRY(n8m.reserve((size_t)(cap + F16P_COL_STEP) * sizeof(float4)));
         }
         if (idx->ntotal > 0) {
-            VSC_HIP(hipMemcpyAsync(nb.p, idx->ref.p, (size_t)idx->ntotal * idx->dpad * 4,
-                                   hipMemcpyDeviceToDevice, idx->stream));
-            if (idx->prefilter) {
+            if (!sq16(idx))
+                VSC_HIP(hipMemcpyAsync(nb.p, idx->ref.p, (size_t)idx->ntotal * idx->dpad * 4,
+                                       hipMemcpyDeviceToDevice, idx->stream));
+            if (keep_half) {
                 // (fragment-major: whole 64-row tiles; the padding rows of the last one are rewritten below)
                 VSC_HIP(hipMemcpyAsync(nh.p, idx->refh.p, (size_t)round_up64(idx->ntotal, 64) * idx->dpadh * 2,
                                        hipMemcpyDeviceToDevice, idx->stream));
@@ -596,6 +724,11 @@ int vsc_index_add(vsc_index_t* idx, const float* x, int64_t n, int x_mem) {
         idx->ref8m = n8m;
         idx->cap_rows = cap;
     }
+    if (sq16(idx)) {
+        VSC_TRY(store_rows(idx, x, src16, n, x_mem, need_rows));
+        idx->ntotal += n;
+        return VSC_OK;
+    }
     float* dst = idx->ref.as<float>() + idx->ntotal * idx->dpad;
     HalfImage h;
     if (idx->prefilter) {
@@ -606,9 +739,43 @@ int vsc_index_add(vsc_index_t* idx, const float* x, int64_t n, int x_mem) {
         h.rows_out = need_rows - idx->ntotal;
         h.dpadh = idx->dpadh;
     }
-    VSC_TRY(pack_into(x, n, idx->dim, x_mem, dst, need_rows - idx->ntotal, idx->dpad, idx->ws, idx->stream, h));
+    if (src16) VSC_TRY(pack_f16_rows(idx, static_cast<const uint16_t*>(x), n, x_mem, dst, need_rows - idx->ntotal, h));
+    else VSC_TRY(pack_into(static_cast<const float*>(x), n, idx->dim, x_mem, dst, need_rows - idx->ntotal, idx->dpad, idx->ws, idx->stream, h));
     VSC_HIP(hipStreamSynchronize(idx->stream));
     idx->ntotal += n;  // (the int8 image catches up in i8_prepare, before the next search)
+    return VSC_OK;
+}
+
+extern "C" {
+
+int vsc_index_add(vsc_index_t* idx, const float* x, int64_t n, int x_mem) { return index_add(idx, x, false, n, x_mem); }
+
+int vsc_index_add_f16(vsc_index_t* idx, const uint16_t* x, int64_t n, int x_mem) { return index_add(idx, x, true, n, x_mem); }
+
+int vsc_index_reconstruct(vsc_index_t* idx, int64_t i0, int64_t n, float* out, int out_mem) {
+    if (!idx || i0 < 0 || n < 0 || i0 + n > idx->ntotal || (n > 0 && !out)) {
+        set_error("vsc_index_reconstruct: invalid argument (rows [%lld, %lld) of %lld)", (long long)i0, (long long)(i0 + n),
+                  (long long)(idx ? idx->ntotal : 0));
+        return VSC_ERR_INVALID;
+    }
+    if (n == 0) return VSC_OK;
+    VSC_HIP(hipSetDevice(idx->device));
+    const int dim = idx->dim;
+    for (int64_t c0 = 0; c0 < n; c0 += DEC_CHUNK_ROWS) {
+        const int64_t rc = std::min(DEC_CHUNK_ROWS, n - c0);
+        float* dst = out + c0 * dim;
+        if (out_mem == VSC_MEM_HOST) {
+            VSC_TRY(idx->ws.dec.reserve((size_t)rc * dim * sizeof(float)));
+            dst = idx->ws.dec.as<float>();
+        }
+        if (sq16(idx))
+            VSC_TRY(launch_decode_rows(idx->refh.as<_Float16>(), idx->dpadh, idx->frag, i0 + c0, rc, idx->ntotal, dst, dim, false, idx->stream));
+        else
+            VSC_TRY(launch_unpack_rows(idx->ref.as<float>() + (i0 + c0) * idx->dpad, idx->dpad, rc, dim, dst, idx->stream));
+        if (out_mem == VSC_MEM_HOST)
+            VSC_HIP(hipMemcpyAsync(out + c0 * dim, dst, (size_t)rc * dim * sizeof(float), hipMemcpyDeviceToHost, idx->stream));
+        VSC_HIP(hipStreamSynchronize(idx->stream));  // (the buffer is reused)
+    }
     return VSC_OK;
 }
 

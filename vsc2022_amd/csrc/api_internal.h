@@ -36,9 +36,14 @@ struct Workspace {
     DevBuf rt8d;            // centred reference image: x . mu and sum |x mu| of the launch's rows
     DevBuf rt8, rt8b;       // ... and its row thresholds in position order (rows sorted by threshold inside a launch);
                             // rt8b: thresholds lowered by the excluded coordinates' contribution, in row order
+    // SQfp16 codec: a bounded range of reference rows decoded to packed fp32 for the exact kernels that read whole
+    // rows (DEC_CHUNK_ROWS rows at most, whatever ntotal is), the "invalid row" flag of an add + the hit-list mark of
+    // a range, and the per-range partial lists of the exact k-NN
+    DevBuf dec, flag, kparts, kpartj;
     DevBuf sample, sk[3], tk[3];  // proven top-K route (api_search.hip): the row sample, its sorted hits, the K + 1 best of the steady run
     void release() {
         stage.release(); qbuf.release(); sample.release();
+        dec.release(); flag.release(); kparts.release(); kpartj.release();
         for (auto& b : sk) b.release();
         for (auto& b : tk) b.release();
         qh.release(); qn.release(); ci.release(); cj.release(); segcnt.release(); rowthr.release(); slices.release();
@@ -75,6 +80,10 @@ using namespace vscmi;
 
 struct vsc_index {
     int dim = 0, dpad = 0, metric = 0, device = 0;
+    // VSC_CODEC_FLAT: `ref` holds the packed fp32 rows.  VSC_CODEC_SQFP16: `ref` is never allocated; the rows live once,
+    // as half floats, in refh / refn (kept whatever `prefilter` and the metric say) and every reader sees their
+    // decoded values
+    int codec = VSC_CODEC_FLAT;
     int64_t ntotal = 0, cap_rows = 0;
     DevBuf ref;
     // fp16 image (dpadh halves per row) and row-norm bounds of the references: the pre-filter of the
@@ -210,6 +219,12 @@ struct AuxTimer {
         a = b = nullptr;
     }
 };
+
+// SQfp16 codec (api.hip): rows per decoded range of the exact readers, and the range itself -- rows [r0, r0 + rows) of
+// the store as packed fp32 in ws.dec, followed by >= 512 zero rows (the tile streams read ahead)
+constexpr int64_t DEC_CHUNK_ROWS = 65536;
+inline bool sq16(const vsc_index* idx) { return idx->codec == VSC_CODEC_SQFP16; }
+int decode_range(vsc_index* idx, int64_t r0, int64_t rows, float** out);
 
 // index upkeep (api.hip)
 int i8_prepare(vsc_index* idx);         // before a search that may use the int8 kernel: bring the image up to date

@@ -30,6 +30,34 @@ static int knn_exact_ip(vsc_index* idx, const float* qp, int64_t nq, int64_t nr,
     SimKnnArgs a{qp, idx->ref.as<float>(), idx->dpad, (int)nq, (int)nr, tq, tr, nchunk, k,
                  idx->ws.parts.as<float>(), idx->ws.partj.as<int32_t>(), idx->knn_first_tile ? 0 : 1};
     hipEvent_t stop;
+    if (sq16(idx)) {
+        // the kernel streams whole packed rows: bounded ranges of the store are decoded for it; a range's partial
+        // lists (refs relative to it) go to their slot among the lists of all ranges, which the merge below treats
+        // like the runs of one launch -- the same (score desc, ref asc) order, the same scores
+        const int nranges = (int)((nr + DEC_CHUNK_ROWS - 1) / DEC_CHUNK_ROWS);
+        const int nch = std::max(1, std::min(nchunk, (int)((std::min(nr, DEC_CHUNK_ROWS) + 127) / 128)));
+        VSC_TRY(idx->ws.kparts.reserve((size_t)nq_pad * nranges * nch * k * 4));
+        VSC_TRY(idx->ws.kpartj.reserve((size_t)nq_pad * nranges * nch * k * 4));
+        VSC_TRY(idx->ws.parts.reserve((size_t)nq_pad * nch * k * 4));
+        VSC_TRY(idx->ws.partj.reserve((size_t)nq_pad * nch * k * 4));
+        for (int rg = 0; rg < nranges; ++rg) {
+            const int64_t j0 = (int64_t)rg * DEC_CHUNK_ROWS, rows = std::min(DEC_CHUNK_ROWS, nr - j0);
+            float* dec = nullptr;
+            VSC_TRY(decode_range(idx, j0, rows, &dec));
+            a.R = dec;
+            a.nr = (int)rows;
+            a.tr = (int)((rows + 127) / 128);
+            a.nchunk = nch;
+            VSC_TRY(prof_begin(idx, &stop));
+            VSC_TRY(launch_sim_knn(a, idx->stream));
+            VSC_TRY(prof_end(idx, stop, 2.0 * (double)nq * (double)rows * (double)idx->dim));
+            VSC_TRY(launch_knn_parts_scatter(a.part_s, a.part_j, nq_pad, nch, k, rg, nranges, (int)j0, idx->ws.kparts.as<float>(),
+                                             idx->ws.kpartj.as<int32_t>(), idx->stream));
+        }
+        KnnMergeArgs m{idx->ws.kparts.as<float>(), idx->ws.kpartj.as<int32_t>(), (int)nq, nranges * nch, k, ds, dj, 0};
+        VSC_TRY(launch_knn_merge(m, idx->stream));
+        return VSC_OK;
+    }
     VSC_TRY(prof_begin(idx, &stop));
     VSC_TRY(launch_sim_knn(a, idx->stream));
     VSC_TRY(prof_end(idx, stop, 2.0 * (double)nq * (double)nr * (double)idx->dim));
@@ -207,7 +235,8 @@ int vsc_index_knn(vsc_index_t* idx, const float* q, int64_t nq, int q_mem, int k
             const int rows = (int)std::min(chunk, nq - r0);
             ScoreMatArgs sm{qp + r0 * idx->dpad, idx->ref.as<float>(), idx->dpad, idx->dim, rows, (int)nr,
                             idx->metric, idx->ws.mat.as<float>()};
-            VSC_TRY(launch_score_matrix(sm, idx->stream));
+            if (sq16(idx)) VSC_TRY(launch_score_matrix_h16(sm, idx->refh.as<_Float16>(), idx->dpadh, idx->frag, idx->stream));
+            else VSC_TRY(launch_score_matrix(sm, idx->stream));
             MatKnnArgs mk{idx->ws.mat.as<float>(), rows, (int)nr, k, idx->ws.parts.as<float>() + r0 * k,
                           idx->ws.partj.as<int32_t>() + r0 * k};
             VSC_TRY(launch_matrix_knn(mk, idx->stream));

@@ -236,6 +236,12 @@ int enqueue_f16(vsc_index* idx, const float* qpacked, int64_t i0, int64_t i1, in
         r.overflow = &ctl->overflow;
         r.row_thr = row_thr;
         r.j0 = (int)nr_begin;
+        if (sq16(idx)) {  // the reference rows come from the fp16 store (sim_f16.hip: rescore_list<SRC>)
+            r.R = nullptr;
+            r.Rh = idx->refh.as<_Float16>();
+            r.dpadh = idx->dpadh;
+            r.rsrc = idx->frag ? 2 : 1;
+        }
         VSC_TRY(prof_begin(idx, &stop, 2));
         // The candidates are compacted out of the waves' segments, sorted by reference row and re-scored as one dense
         // list (sim_f16.hip, "candidates ordered by reference row"): 74 -> 54 ms per bench step, k-NN k = 20 140 ->
@@ -331,6 +337,26 @@ static int enqueue_batch(vsc_index* idx, const float* qpacked, int64_t i0, int64
         a.cap = cap;
         a.overflow = &ctl->overflow;
         hipEvent_t stop;
+        if (sq16(idx)) {
+            // the kernel streams whole packed rows: bounded ranges of the store are decoded for it, one after the other;
+            // the hits a range appends carry refs relative to it and get the range's offset afterwards
+            VSC_TRY(idx->ws.flag.reserve(16));
+            unsigned long long* mark = idx->ws.flag.as<unsigned long long>() + 1;
+            for (int64_t j0 = 0; j0 < idx->ntotal; j0 += DEC_CHUNK_ROWS) {
+                const int64_t rows = std::min(DEC_CHUNK_ROWS, idx->ntotal - j0);
+                float* dec = nullptr;
+                VSC_TRY(decode_range(idx, j0, rows, &dec));
+                a.R = dec;
+                a.nr = (int)rows;
+                a.tr = (int)((rows + 127) / 128);
+                if (j0 > 0) VSC_TRY(launch_hits_mark(&ctl->n, mark, idx->stream));
+                VSC_TRY(prof_begin(idx, &stop));
+                VSC_TRY(launch_sim_thresh(a, idx->stream));
+                VSC_TRY(prof_end(idx, stop, 2.0 * (double)nqb * (double)rows * (double)idx->dim));
+                if (j0 > 0) VSC_TRY(launch_hits_add_offset(a.out_j, mark, &ctl->n, cap, (int)j0, idx->stream));
+            }
+            return VSC_OK;
+        }
         VSC_TRY(prof_begin(idx, &stop));
         VSC_TRY(launch_sim_thresh(a, idx->stream));
         VSC_TRY(prof_end(idx, stop, 2.0 * (double)nqb * (double)idx->ntotal * (double)idx->dim));
@@ -344,7 +370,8 @@ static int enqueue_batch(vsc_index* idx, const float* qpacked, int64_t i0, int64
         const int rows = (int)std::min(chunk, i1 - r0);
         ScoreMatArgs m{qpacked + r0 * idx->dpad, idx->ref.as<float>(), idx->dpad, idx->dim, rows, (int)nr,
                        idx->metric, idx->ws.mat.as<float>()};
-        VSC_TRY(launch_score_matrix(m, idx->stream));
+        if (sq16(idx)) VSC_TRY(launch_score_matrix_h16(m, idx->refh.as<_Float16>(), idx->dpadh, idx->frag, idx->stream));
+        else VSC_TRY(launch_score_matrix(m, idx->stream));
         MatThreshArgs t{idx->ws.mat.as<float>(), rows, (int)nr, (int)r0, &ctl->radius,
                         idx->ws.hA[0].as<int32_t>(), idx->ws.hA[1].as<int32_t>(), idx->ws.hA[2].as<float>(),
                         &ctl->n, cap, &ctl->overflow};

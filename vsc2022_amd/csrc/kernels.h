@@ -90,6 +90,9 @@ struct RescoreArgs {
     // the launch searched the reference rows [j0, j0 + nr): the kernels' images were handed over from row j0 on, the
     // candidate list holds refs RELATIVE to it (cand_compact / the segment-wise exact stage add j0 back)
     int j0 = 0;
+    // SQfp16 codec: the reference rows are read from the fp16 store instead of R (rsrc: 0 = R, packed fp32; 1 = Rh in
+    // natural layout; 2 = Rh fragment-major) and converted in registers; the chain is the same
+    const _Float16* Rh = nullptr; int dpadh = 0; int rsrc = 0;
 };
 // fp16 screen of the int8 route's candidates (sim_f16.hip): the pair list sorted by reference row in, the pairs whose
 // fp16 score + error bound still reaches the threshold out
@@ -197,6 +200,15 @@ int launch_row_normalize(const float*, int64_t, int, float*, hipStream_t);
 size_t tn_state_bytes_host(int, int, int, int idx_bytes = 2);
 int launch_tn_pairs(const TnPairArgs&, size_t, hipStream_t);
 int launch_tn_sims(const TnSimsArgs&, hipStream_t);
+// SQfp16 codec (codec_f16.hip)
+int launch_encode_rows(const void*, bool, int64_t, int, _Float16*, float*, int64_t, int64_t, int, bool, int*, hipStream_t);
+int launch_decode_rows(const _Float16*, int, bool, int64_t, int64_t, int64_t, float*, int, bool, hipStream_t);
+int launch_unpack_rows(const float*, int, int64_t, int, float*, hipStream_t);
+int launch_half_to_float(const _Float16*, int64_t, float*, hipStream_t);
+int launch_score_matrix_h16(const ScoreMatArgs&, const _Float16*, int, bool, hipStream_t);
+int launch_hits_mark(const unsigned long long*, unsigned long long*, hipStream_t);
+int launch_hits_add_offset(int32_t*, const unsigned long long*, const unsigned long long*, long long, int, hipStream_t);
+int launch_knn_parts_scatter(const float*, const int32_t*, int64_t, int, int, int, int, int, float*, int32_t*, hipStream_t);
 
 
 }  // namespace vscmi

@@ -514,7 +514,22 @@ __device__ __forceinline__ void flush_hits(const RescoreArgs& a, WaveHits& buf, 
     pend = 0;
 }
 
+typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
+// one 16-byte piece of the fp16 store (k ascending) -> the even / odd operands of the packed query's group of 8
+__device__ __forceinline__ void half_piece(const f16x8_t h, f32x4& even, f32x4& odd) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        even[s] = (float)h[2 * s];
+        odd[s] = (float)h[2 * s + 1];
+    }
+}
+
 // candidates of one list; thread x serves candidate x >> 2 (x0 = first thread index, `step` threads apart)
+// SRC: where the reference row comes from -- 0 the packed fp32 image (Flat codec), 1 / 2 the SQfp16 store in natural /
+// fragment-major layout.  The store keeps natural k order inside a 16-byte piece: lane g's piece of round rd
+// (k = 32 rd + 8 g .. + 7) is ONE 16-byte load, its even / odd halves are the operands of the packed query's
+// [k0 k2 k4 k6 | k1 k3 k5 k7]; the conversions are exact and the chain is the same.
+template <int SRC>
 __device__ __forceinline__ void rescore_list(const RescoreArgs& a, float radius, const int32_t* ci,
                                              const int32_t* cj, long long n, long long x0, long long step,
                                              WaveHits& buf, int& pend, const int* fill = nullptr, int shift = 0) {
@@ -530,11 +545,30 @@ __device__ __forceinline__ void rescore_list(const RescoreArgs& a, float radius,
         if (a.perm && valid) i = a.perm_i0 + a.perm[i - a.perm_i0];  // position inside a permuted int8 launch -> row
         const f32x4* q = reinterpret_cast<const f32x4*>(a.Q + (int64_t)i * a.dpad) + 2 * g;
         const f32x4* r = reinterpret_cast<const f32x4*>(a.R + (int64_t)j * a.dpad) + 2 * g;
+        // (fp16 store: piece 4 rd + g of row j; fragment-major pieces of one row lie 512 B / 2 KiB apart)
+        const f16x8_t* rh = reinterpret_cast<const f16x8_t*>(a.Rh) +
+                            (SRC == 2 ? (int64_t)(j >> 6) * (a.dpadh / 16) * 128 + ((j >> 5) & 1) * 64 + (j & 31) + (g >> 1) * 128 + (g & 1) * 32
+                                      : (int64_t)j * (a.dpadh / 8) + g);
+        constexpr int RH_STEP = SRC == 2 ? 256 : 4;  // pieces between two rounds of one lane
         float acc = 0.0f;  // the live value sits in lane 0 of the quad at the top of every round
-        f32x4 qe = q[0], qo = q[1], re = r[0], ro = r[1];
+        f32x4 qe = q[0], qo = q[1], re, ro;
+        if constexpr (SRC == 0) {
+            re = r[0];
+            ro = r[1];
+        } else {
+            half_piece(rh[0], re, ro);
+        }
         for (int rd = 0; rd < rounds; ++rd) {
             const int nx = rd + 1 < rounds ? rd + 1 : rd;  // prefetch the next round's groups
-            const f32x4 nqe = q[8 * nx], nqo = q[8 * nx + 1], nre = r[8 * nx], nro = r[8 * nx + 1];
+            const f32x4 nqe = q[8 * nx], nqo = q[8 * nx + 1];
+            f32x4 nre, nro;
+            f16x8_t nrh;
+            if constexpr (SRC == 0) {
+                nre = r[8 * nx];
+                nro = r[8 * nx + 1];
+            } else {
+                nrh = rh[(int64_t)RH_STEP * nx];
+            }
 #pragma unroll
             for (int gp = 0; gp < 4; ++gp) {
                 float v = acc;
@@ -548,8 +582,12 @@ __device__ __forceinline__ void rescore_list(const RescoreArgs& a, float radius,
             }
             qe = nqe;
             qo = nqo;
-            re = nre;
-            ro = nro;
+            if constexpr (SRC == 0) {
+                re = nre;
+                ro = nro;
+            } else {
+                half_piece(nrh, re, ro);
+            }
         }
         const bool hit = valid && g == 0 && (a.row_thr ? acc >= a.row_thr[i] : acc > radius);
         const unsigned long long m = __ballot(hit);  // <= 16 hits per pass
@@ -569,6 +607,7 @@ __device__ __forceinline__ void rescore_list(const RescoreArgs& a, float radius,
 #endif
 constexpr int RESCORE_SHARE = VSC_RESCORE_SHARE;
 
+template <int SRC>
 __global__ __launch_bounds__(256) void rescore_kernel(RescoreArgs a) {
     // After an overflow the candidate list has holes (a wave whose tail reservation did not fit skipped its
     // writes but the tail counter moved on): the host reruns the search with larger buffers, so do nothing
@@ -585,14 +624,14 @@ __global__ __launch_bounds__(256) void rescore_kernel(RescoreArgs a) {
         const int seg = blockIdx.x / RESCORE_SHARE, part = blockIdx.x % RESCORE_SHARE;
         const int n = min(a.seg_count[seg], a.seg_cap);
         if (part == 0) seen += (unsigned long long)n;
-        rescore_list(a, radius, a.cand_i + (int64_t)seg * a.seg_cap, a.cand_j + (int64_t)seg * a.seg_cap, n,
+        rescore_list<SRC>(a, radius, a.cand_i + (int64_t)seg * a.seg_cap, a.cand_j + (int64_t)seg * a.seg_cap, n,
                      part * 256 + threadIdx.x, 256 * RESCORE_SHARE, buf, pend);
     }
     // shared tail (normally empty)
     const unsigned long long nt_all = *a.tail_count;
     const long long nt = nt_all < (unsigned long long)a.tail_cap ? (long long)nt_all : a.tail_cap;
     if (nt > 0) {
-        rescore_list(a, radius, a.cand_i + a.tail_base, a.cand_j + a.tail_base, nt,
+        rescore_list<SRC>(a, radius, a.cand_i + a.tail_base, a.cand_j + a.tail_base, nt,
                      (long long)blockIdx.x * 256 + threadIdx.x, (long long)gridDim.x * 256, buf, pend, a.tail_fill,
                      a.tail_shift);
         if (blockIdx.x == 0) seen += (unsigned long long)nt;
@@ -728,6 +767,7 @@ int launch_f16_screen(const ScreenArgs& a, hipStream_t stream) {
 }
 
 // n_dev: the list's length lives on the device (the fp16 screen's survivors; n = an upper bound for the grid)
+template <int SRC>
 __global__ __launch_bounds__(256) void rescore_dense_kernel(RescoreArgs a, const uint32_t* __restrict__ sj,
                                                             const uint32_t* __restrict__ si, long long n,
                                                             const unsigned long long* __restrict__ n_dev) {
@@ -739,7 +779,7 @@ __global__ __launch_bounds__(256) void rescore_dense_kernel(RescoreArgs a, const
     const float radius = a.row_thr ? 0.0f : *a.radius;
     a.perm = nullptr;  // (rows already)
     a.j0 = 0;          // (absolute reference rows already: cand_compact added the launch's offset)
-    rescore_list(a, radius, reinterpret_cast<const int32_t*>(si), reinterpret_cast<const int32_t*>(sj), n,
+    rescore_list<SRC>(a, radius, reinterpret_cast<const int32_t*>(si), reinterpret_cast<const int32_t*>(sj), n,
                  (long long)blockIdx.x * 256 + threadIdx.x, (long long)gridDim.x * 256, buf, pend);
     flush_hits(a, buf, pend);
     if (blockIdx.x == 0 && threadIdx.x == 0 && !n_dev) atomicAdd(a.n_cand_total, (unsigned long long)n);
@@ -788,7 +828,9 @@ int launch_rescore_dense(const RescoreArgs& a, const uint32_t* sj, const uint32_
                          const unsigned long long* n_dev) {
     if (n > 0) {
         const unsigned grid = (unsigned)std::min<long long>(16384, (n * 4 + 255) / 256);
-        hipLaunchKernelGGL(rescore_dense_kernel, dim3(grid), dim3(256), 0, stream, a, sj, si, n, n_dev);
+        if (a.rsrc == 0) hipLaunchKernelGGL(rescore_dense_kernel<0>, dim3(grid), dim3(256), 0, stream, a, sj, si, n, n_dev);
+        else if (a.rsrc == 1) hipLaunchKernelGGL(rescore_dense_kernel<1>, dim3(grid), dim3(256), 0, stream, a, sj, si, n, n_dev);
+        else hipLaunchKernelGGL(rescore_dense_kernel<2>, dim3(grid), dim3(256), 0, stream, a, sj, si, n, n_dev);
     }
     hipLaunchKernelGGL(tail_reset_kernel, dim3(1), dim3(1), 0, stream, a.tail_count);
     VSC_HIP(hipGetLastError());
@@ -797,7 +839,10 @@ int launch_rescore_dense(const RescoreArgs& a, const uint32_t* sj, const uint32_
 
 int launch_rescore(const RescoreArgs& a, hipStream_t stream) {
     if (a.n_seg <= 0) return VSC_OK;
-    hipLaunchKernelGGL(rescore_kernel, dim3((unsigned)a.n_seg * RESCORE_SHARE), dim3(256), 0, stream, a);
+    const dim3 grid((unsigned)a.n_seg * RESCORE_SHARE);
+    if (a.rsrc == 0) hipLaunchKernelGGL(rescore_kernel<0>, grid, dim3(256), 0, stream, a);
+    else if (a.rsrc == 1) hipLaunchKernelGGL(rescore_kernel<1>, grid, dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(rescore_kernel<2>, grid, dim3(256), 0, stream, a);
     hipLaunchKernelGGL(tail_reset_kernel, dim3(1), dim3(1), 0, stream, a.tail_count);
     VSC_HIP(hipGetLastError());
     return VSC_OK;

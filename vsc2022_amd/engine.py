@@ -109,7 +109,9 @@ class DeviceScoreNormalizer:
     reference's column even on near-ties).
     """
 
-    def __init__(self, noise: torch.Tensor, beta: float = 1.0, l2_normalize: bool = True, replace_dim: bool = True):
+    def __init__(self, noise: torch.Tensor, beta: float = 1.0, l2_normalize: bool = True, replace_dim: bool = True,
+                 codec: str = "Flat"):
+        """codec: how the noise index stores its rows ("Flat" / "SQfp16", vsc.index.FlatIndex)."""
         self.beta, self.l2_normalize = float(beta), bool(l2_normalize)
         dev = noise.device
         self.sel = None
@@ -118,7 +120,7 @@ class DeviceScoreNormalizer:
             keep = [c for c in range(noise.shape[1]) if c != weakest]
             self.sel = torch.tensor(keep, dtype=torch.int64, device=dev)
         noise = self._prepare(noise)
-        self.noise_index = FlatIndex(int(noise.shape[1]), _lib.METRIC_INNER_PRODUCT, dev.index)
+        self.noise_index = FlatIndex(int(noise.shape[1]), _lib.METRIC_INNER_PRODUCT, dev.index, codec=codec)
         if os.environ.get("VSC_TORCH_STREAM", "1") != "0":
             self.noise_index.use_torch_stream()
         self.noise_index.add(noise)
@@ -152,8 +154,12 @@ class DeviceMatcher:
     *_off: int64 numpy row offsets per video.
     """
 
-    def __init__(self, ref_feats, r_off: np.ndarray, device: Optional[int] = None, tn_ref_feats=None):
-        """tn_ref_feats: reference rows the ALIGNER sees when they differ from the rows that are searched
+    def __init__(self, ref_feats, r_off: np.ndarray, device: Optional[int] = None, tn_ref_feats=None, codec: str = "Flat"):
+        """codec: how the search index (and the column index of the column-sharded mode) stores the reference rows
+        ("Flat" / "SQfp16", vsc.index.FlatIndex).  The codec belongs to the index: the Temporal-Network context keeps its
+        own fp32 copy of the descriptors it is given, as localisation does in the reference.
+
+        tn_ref_feats: reference rows the ALIGNER sees when they differ from the rows that are searched
         (vsc/baseline/sscd_baseline.py:128-135: without score normalisation the reference searches the descriptors as they
         are and localises on their L2-normalised copies)."""
         self.device = _lib.default_device() if device is None else int(device)
@@ -164,7 +170,8 @@ class DeviceMatcher:
         self.ref_feats = self._as_dev(ref_feats)
         self.tn_ref_feats = self.ref_feats if tn_ref_feats is None else self._as_dev(tn_ref_feats)
         self.dim = int(self.ref_feats.shape[1])
-        self.index = FlatIndex(self.dim, _lib.METRIC_INNER_PRODUCT, self.device)
+        self.codec = codec
+        self.index = FlatIndex(self.dim, _lib.METRIC_INNER_PRODUCT, self.device, codec=codec)
         # the library's handles run on torch's current stream (vsc_index_set_stream & co., round 5): no device-wide
         # synchronisation in front of every call (VSC_TORCH_STREAM=0: the handles' own streams + synchronisations)
         self.torch_stream = os.environ.get("VSC_TORCH_STREAM", "1") != "0"
@@ -486,7 +493,7 @@ class DeviceMatcher:
                 c1 = nr
             col_index = getattr(self, "_col_index", None)
             if col_index is None or self._col_range != (c0, c1):
-                col_index = FlatIndex(self.dim, _lib.METRIC_INNER_PRODUCT, self.device)
+                col_index = FlatIndex(self.dim, _lib.METRIC_INNER_PRODUCT, self.device, codec=self.codec)
                 if self.torch_stream:
                     col_index.use_torch_stream()
                 col_index.set_option("sort_hits", 0)   # (a batch's hits join a list that is sorted once, at the end)

@@ -44,7 +44,7 @@ class RefShardedIndex:
         self.device = device if device is not None else torch.device("cpu")
 
     @classmethod
-    def build(cls, ref_rows, dim: int, metric: int, device_index: int, group=None) -> "RefShardedIndex":
+    def build(cls, ref_rows, dim: int, metric: int, device_index: int, group=None, codec: str = "Flat") -> "RefShardedIndex":
         """Shard `ref_rows` ([n, dim] array / tensor that every rank can see, e.g. an np.memmap of the
         descriptor file) by `dist.shard_ranges` and add this rank's rows to a FlatIndex on its GPU."""
         from vsc2022_amd.vsc.index import FlatIndex
@@ -52,7 +52,7 @@ class RefShardedIndex:
         rank, world = vdist._world(group)
         n_total = int(ref_rows.shape[0])
         lo, hi = vdist.shard_ranges(n_total, world)[rank]
-        idx = FlatIndex(dim, metric, device_index)
+        idx = FlatIndex(dim, metric, device_index, codec=codec)  # ("Flat" / "SQfp16": how the shard stores its rows)
         if hi > lo:
             idx.add(ref_rows[lo:hi])
         return cls(idx, lo, n_total, group, torch.device("cuda", device_index))

@@ -123,18 +123,23 @@ class FlatIndex:
     """
 
     def __init__(self, d: int, metric: int = METRIC_INNER_PRODUCT, device: Optional[int] = None,
-                 options: Optional[dict] = None):
-        """options: {name: value} applied with `set_option` while the index is still empty -- the explicit form of the
+                 options: Optional[dict] = None, codec: str = "Flat"):
+        """codec: "Flat" (fp32 rows) or "SQfp16" (faiss IndexScalarQuantizer, QT_fp16: the rows are stored as half floats
+        and every search sees their decoded values -- include/vscmi.h, vsc_index_create_codec).
+
+        options: {name: value} applied with `set_option` while the index is still empty -- the explicit form of the
         VSC_* environment switches (include/vscmi.h), including the ones that decide which images of the reference
         rows are kept ("prefilter", "i8", "f16_kernel", "i8_exclude") and can only be set before the first `add`."""
         if metric not in (METRIC_INNER_PRODUCT, METRIC_L2):
             raise ValueError(f"unsupported metric {metric}")
+        codec_id = _lib.codec_id(codec)  # (NotImplementedError before any device is needed)
+        self.codec = codec
         self.d = int(d)
         self.metric_type = metric
         self.device = _lib.default_device() if device is None else int(device)
         self._h = ctypes.c_void_p()
         self._stream = None  # None: the handle's own stream; else the hipStream_t value it was bound to (0 = default stream)
-        _lib.check(_lib.lib().vsc_index_create(self.d, metric, self.device, ctypes.byref(self._h)))
+        _lib.check(_lib.lib().vsc_index_create_codec(self.d, metric, self.device, codec_id, ctypes.byref(self._h)))
         for name, value in (options or {}).items():
             self.set_option(name, value)
 
@@ -208,9 +213,48 @@ class FlatIndex:
         p, mem = _lib.ptr(x)
         return p, mem, int(x.shape[0]), x
 
+    def _half_rows(self, x):
+        """Rows that are already half floats (float16 numpy array, half torch tensor) as (pointer, mem kind, n,
+        keep-alive); None for everything else."""
+        if isinstance(x, np.ndarray):
+            if x.dtype != np.float16:
+                return None
+            x = np.ascontiguousarray(x)
+        elif hasattr(x, "data_ptr"):
+            import torch
+
+            if x.dtype != torch.float16:
+                return None
+            x = x.contiguous()
+            if x.is_cuda:
+                self._after_torch(x.device)
+        else:
+            return None
+        if x.ndim != 2 or x.shape[1] != self.d:
+            raise ValueError(f"expected [n, {self.d}] features, got {tuple(x.shape)}")
+        p, mem = _lib.ptr(x)
+        return p, mem, int(x.shape[0]), x
+
     def add(self, x):
+        """faiss index.add.  Half-float rows go down as they are (vsc_index_add_f16): an SQfp16 index stores them
+        without any fp32 copy, a Flat index decodes them on the device."""
+        half = self._half_rows(x)
+        if half is not None:
+            p, mem, n, keep = half
+            _lib.check(_lib.lib().vsc_index_add_f16(self._h, p, n, mem))
+            return
         p, mem, n, keep = self._rows(x)
         _lib.check(_lib.lib().vsc_index_add(self._h, p, n, mem))
+
+    def reconstruct_n(self, i0: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """faiss index.reconstruct_n: fp32 [n, d] of rows [i0, i0 + n) as the searches see them (SQfp16: decoded)."""
+        i0 = int(i0)
+        n = self.ntotal - i0 if n is None else int(n)
+        if i0 < 0 or n < 0 or i0 + n > self.ntotal:
+            raise ValueError(f"rows [{i0}, {i0 + n}) are not inside the index ({self.ntotal} rows)")
+        out = np.empty((n, self.d), dtype=np.float32)
+        _lib.check(_lib.lib().vsc_index_reconstruct(self._h, i0, n, out.ctypes.data, _lib.MEM_HOST))
+        return out
 
     def search(self, x, k: int, device_out: bool = False):
         """faiss index.search: (D float32 [n, k], I int64 [n, k]); with device_out torch tensors that never leave
@@ -381,12 +425,10 @@ class VideoIndex:
 
     def __init__(self, dim: int, codec_str: str = "Flat", metric: int = METRIC_INNER_PRODUCT,
                  device: Optional[int] = None):
-        if codec_str != "Flat":
-            raise NotImplementedError(
-                f"codec {codec_str!r}: the MI355X engine implements the flat (exhaustive) index only"
-            )
+        _lib.codec_id(codec_str)  # "Flat" or "SQfp16"; NotImplementedError for every other factory string
         self.dim = dim
-        self.index = FlatIndex(dim, metric, device)
+        self.codec_str = codec_str
+        self.index = FlatIndex(dim, metric, device, codec=codec_str)
         self.video_metadata = {}
         self._video_ids: list = []
         self._vid_ordinal = {}
@@ -421,7 +463,11 @@ class VideoIndex:
         del base
         self._row2vid = np.concatenate([self._row2vid, ordinals[layout.row2vid]])
         self._row2frame = np.concatenate([self._row2frame, layout.row2frame])
-        self.index.add(VideoLayout.features(db))
+        if all(isinstance(v.feature, np.ndarray) and v.feature.dtype == np.float16 for v in db):
+            # descriptors stored as half floats (--store_fp16) go down as they are
+            self.index.add(np.concatenate([v.feature for v in db], axis=0))
+        else:
+            self.index.add(VideoLayout.features(db))
 
     # -- engine-level search returning arrays
     def search_hits(self, queries: List[VideoFeature], global_k: int, device_out: bool = False):
