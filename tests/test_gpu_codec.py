@@ -236,6 +236,77 @@ def test_exact_kernels_over_several_decoded_ranges(gpu, orc):
         assert (I[:, 0] >= 65536).mean() > 0.8   # (the rest: rows that hold the large planted values of codec_rows)
 
 
+def test_int8_upkeep_over_several_decoded_ranges(gpu, orc):
+    """The int8 image's upkeep (per-coordinate min / max, centre, quantisation) reads an SQfp16 store in decoded ranges
+    of 65536 rows and a Flat index in one piece: 65536 + 640 rows, one coordinate constant (excluded), centring forced,
+    added in two calls that split at row 65000.  The upkeep is lazy -- the first search catches up on every row added
+    so far -- so with both adds first it walks [0, 66176) as the ranges [0, 65536) and [65536, 66176); with a search
+    between the adds (second leg) the catch-up of the second add starts at row 65000, not at a range boundary.
+    Both walks must leave the same excluded set, centre and int8 image: the searches are bit-identical AND the global
+    top-K and the k-NN hand the same number of candidates to the exact stage.  (A range search does not write the
+    candidate counter; there the results and the int8 launches are compared.  No option reports the excluded set
+    itself: a coordinate kept in one index's image and left out of the other's would show in the candidate counts.)"""
+    d, nq, nr = 32, 256, 65536 + 640
+    q, r = cr.rows(71, nq, d), cr.rows(72, nr, d)
+    r[:, 5] = np.float32(0.7001)   # (not a half: the agreement must hold on the DECODED values)
+    q[::4] = r[65300:65300 + nq // 4] * np.float32(0.999)   # best matches on both sides of the range boundary
+    q[1::8] = r[65600:65600 + nq // 8]
+    rd = dec(r)
+    opts = dict(prefilter=2, i8=2, i8_center=2)
+    sq, flat = make(d, "SQfp16", opts), make(d, "Flat", opts)
+    sq.add(r[:65000]); sq.add(r[65000:])
+    flat.add(rd[:65000]); flat.add(rd[65000:])
+    srt = np.sort(orc.scores(q, rd).ravel())[::-1]
+
+    def same_work(what, sq=sq, flat=flat, counts_candidates=True):
+        a, b = sq.profile_read(reset=True), flat.profile_read(reset=True)
+        print(f"\n{what}: candidates SQfp16 {a['candidates']}, Flat {b['candidates']}; int8 launches {a['i8_launches']} / {b['i8_launches']}")
+        if counts_candidates:
+            assert a["candidates"] == b["candidates"] and a["candidates"] > 0, (what, a["candidates"], b["candidates"])
+        assert a["i8_launches"] > 0 and b["i8_launches"] > 0 and a["i8_launches"] == b["i8_launches"], (what, a, b)
+        assert sq.get_option("i8_fallbacks") == 0 and flat.get_option("i8_fallbacks") == 0
+
+    K = 3000
+    got, ref = sq.global_topk(q, K), flat.global_topk(q, K)
+    oi, oj, os_, info = orc.global_threshold_search(q, rd, K, IP, return_info=True)
+    same_hits(got, (oi, oj, os_))
+    same_hits(got, ref)
+    assert np.float32(got[3]) == np.float32(info["radius"]) == np.float32(ref[3])
+    same_work("global top-K")
+    assert sq.get_option("i8_center_on") == 1.0 and flat.get_option("i8_center_on") == 1.0
+
+    radius = float(srt[2000])
+    lims, D, I = sq.range_search(q, radius)
+    ol, oD, oI = orc.range_search(q, rd, radius, IP)
+    fl, fD, fI = flat.range_search(q, radius)
+    assert len(D) > 0 and (I >= 65536).any() and (I < 65536).any()
+    assert np.array_equal(lims, ol) and np.array_equal(I, oI) and np.array_equal(bits(D), bits(oD))
+    assert np.array_equal(lims, fl) and np.array_equal(I, fI) and np.array_equal(bits(D), bits(fD))
+    same_work("range search", counts_candidates=False)
+
+    for k in (1, 5):
+        D, I = sq.search(q, k)
+        oD, oI = orc.knn(q, rd, k, IP)
+        fD, fI = flat.search(q, k)
+        assert np.array_equal(I, oI) and np.array_equal(bits(D), bits(oD))
+        assert np.array_equal(I, fI) and np.array_equal(bits(D), bits(fD))
+        same_work(f"k-NN k = {k}")
+
+    # second leg: a search between the two adds, so that the second add's catch-up starts at row 65000
+    sq2, flat2 = make(d, "SQfp16", opts, rows=r[:65000]), make(d, "Flat", opts, rows=rd[:65000])
+    D, I = sq2.search(q, 1)
+    oD, oI = orc.knn(q, rd[:65000], 1, IP)
+    fD, fI = flat2.search(q, 1)
+    assert np.array_equal(I, oI) and np.array_equal(bits(D), bits(oD))
+    assert np.array_equal(I, fI) and np.array_equal(bits(D), bits(fD))
+    same_work("k-NN k = 1 on the first add", sq2, flat2)
+    sq2.add(r[65000:]); flat2.add(rd[65000:])
+    got, ref = sq2.global_topk(q, K), flat2.global_topk(q, K)
+    same_hits(got, (oi, oj, os_))
+    same_hits(got, ref)
+    same_work("global top-K after the second add", sq2, flat2)
+
+
 # ------------------------------------------------------------------------------------------------ 3. not an alias
 @pytest.mark.parametrize("d", [256, 512])
 def test_codec_rounds_and_halves_the_memory(gpu, d):

@@ -433,8 +433,20 @@ int decode_range(vsc_index* idx, int64_t r0, int64_t rows, float** out) {
     return VSC_OK;
 }
 
-// (Re)write rows [row0, row0 + rows) of the int8 image and their meta from the packed fp32 rows, with the index's
-// current set of excluded coordinates; the first `count_rows - row0` of them enter the looseness statistic.
+int ref_range_count(const vsc_index* idx, int64_t, int64_t rows) {
+    return sq16(idx) ? (int)((rows + DEC_CHUNK_ROWS - 1) / DEC_CHUNK_ROWS) : 1;
+}
+int for_ref_ranges(vsc_index* idx, int64_t r0, int64_t rows, const RefRangeFn& fn) {
+    if (!sq16(idx)) return fn(idx->ref.as<float>() + r0 * idx->dpad, r0, rows);
+    for (int64_t c0 = r0; c0 < r0 + rows; c0 += DEC_CHUNK_ROWS) {
+        const int64_t rc = std::min(DEC_CHUNK_ROWS, r0 + rows - c0);
+        float* dec = nullptr;
+        VSC_TRY(decode_range(idx, c0, rc, &dec));
+        VSC_TRY(fn(dec, c0, rc));
+    }
+    return VSC_OK;
+}
+
 // The centre as the kernels read it: packed order, zero on the coordinates the image leaves out.
 static int i8_upload_centre(vsc_index* idx) {
     if (!idx->i8_mu_on) return VSC_OK;
@@ -455,27 +467,19 @@ static int i8_decide_centre(vsc_index* idx, int64_t rows) {
     idx->i8_mu_on = false;
     if (idx->i8_center == 0 || rows <= 0) return VSC_OK;
     const int dpad = idx->dpad;
-    VSC_TRY(idx->ws.tmp.reserve((size_t)2 * dpad * sizeof(double)));
-    double* d_sum = idx->ws.tmp.as<double>();
-    std::vector<double> h((size_t)2 * dpad);
-    if (sq16(idx)) {
-        // the decoded values, range by range; the ranges' sums are added up on the host
-        std::vector<double> part(h.size());
-        std::fill(h.begin(), h.end(), 0.0);
-        for (int64_t c0 = 0; c0 < rows; c0 += DEC_CHUNK_ROWS) {
-            const int64_t rc = std::min(DEC_CHUNK_ROWS, rows - c0);
-            float* dec = nullptr;
-            VSC_TRY(decode_range(idx, c0, rc, &dec));
-            VSC_TRY(launch_col_sums(dec, rc, dpad, d_sum, d_sum + dpad, idx->stream));
-            VSC_HIP(hipMemcpyAsync(part.data(), d_sum, part.size() * sizeof(double), hipMemcpyDeviceToHost, idx->stream));
-            VSC_HIP(hipStreamSynchronize(idx->stream));
+    VSC_TRY(idx->ws.sort.tmp.reserve((size_t)2 * dpad * sizeof(double)));
+    double* d_sum = idx->ws.sort.tmp.as<double>();
+    // column sums and sums of squares, range by range; the first range's sums are taken as they are, later ones added
+    std::vector<double> h((size_t)2 * dpad), part(h.size());
+    VSC_TRY(for_ref_ranges(idx, 0, rows, [&](const float* src, int64_t first, int64_t n) -> int {
+        std::vector<double>& dst = first == 0 ? h : part;
+        VSC_TRY(launch_col_sums(src, n, dpad, d_sum, d_sum + dpad, idx->stream));
+        VSC_HIP(hipMemcpyAsync(dst.data(), d_sum, dst.size() * sizeof(double), hipMemcpyDeviceToHost, idx->stream));
+        VSC_HIP(hipStreamSynchronize(idx->stream));
+        if (first > 0)
             for (size_t e = 0; e < h.size(); ++e) h[e] += part[e];
-        }
-    } else {
-    VSC_TRY(launch_col_sums(idx->ref.as<float>(), rows, dpad, d_sum, d_sum + dpad, idx->stream));
-    VSC_HIP(hipMemcpyAsync(h.data(), d_sum, h.size() * sizeof(double), hipMemcpyDeviceToHost, idx->stream));
-    VSC_HIP(hipStreamSynchronize(idx->stream));
-    }
+        return VSC_OK;
+    }));
     idx->i8_mu_host.assign((size_t)dpad, 0.0f);
     double mu2 = 0.0, e2 = 0.0;
     bool finite = true;
@@ -497,6 +501,8 @@ static int i8_decide_centre(vsc_index* idx, int64_t rows) {
     return i8_upload_centre(idx);
 }
 
+// (Re)write rows [row0, row0 + rows) of the int8 image and their meta from the packed fp32 rows, with the index's
+// current set of excluded coordinates; the first `count_rows - row0` of them enter the looseness statistic.
 static int i8_quantise(vsc_index* idx, int64_t row0, int64_t rows, int64_t count_rows) {
     if (rows <= 0) return VSC_OK;
     if (idx->i8_mu_on) {
@@ -505,18 +511,11 @@ static int i8_quantise(vsc_index* idx, int64_t row0, int64_t rows, int64_t count
         for (int c = 0; same && c < idx->i8_ex.n; ++c) same = idx->i8_mu_ex.idx[c] == idx->i8_ex.idx[c];
         if (!same) VSC_TRY(i8_upload_centre(idx));
     }
-    if (sq16(idx)) {
-        // from the decoded values, range by range (the kernel indexes its source by absolute row)
-        for (int64_t c0 = row0; c0 < row0 + rows; c0 += DEC_CHUNK_ROWS) {
-            const int64_t rc = std::min(DEC_CHUNK_ROWS, row0 + rows - c0);
-            float* dec = nullptr;
-            VSC_TRY(decode_range(idx, c0, rc, &dec));
-            VSC_TRY(launch_quant_ref_frag(dec - c0 * idx->dpad, idx->dpad, idx->ref8.p, idx->ref8m.as<float4>(), c0, rc, idx->dpad8,
-                                          idx->i8_ex, idx->i8_mu_on ? idx->i8_mu.as<float>() : nullptr, idx->stream));
-        }
-    } else
-    VSC_TRY(launch_quant_ref_frag(idx->ref.as<float>(), idx->dpad, idx->ref8.p, idx->ref8m.as<float4>(), row0, rows,
-                                  idx->dpad8, idx->i8_ex, idx->i8_mu_on ? idx->i8_mu.as<float>() : nullptr, idx->stream));
+    VSC_TRY(for_ref_ranges(idx, row0, rows, [&](const float* src, int64_t first, int64_t n) -> int {
+        // (the kernel indexes its source by absolute row: hand it where row 0 would lie)
+        return launch_quant_ref_frag(src - first * idx->dpad, idx->dpad, idx->ref8.p, idx->ref8m.as<float4>(), first, n, idx->dpad8,
+                                     idx->i8_ex, idx->i8_mu_on ? idx->i8_mu.as<float>() : nullptr, idx->stream);
+    }));
     const int64_t real = std::max<int64_t>(0, std::min(row0 + rows, count_rows) - row0);
     VSC_TRY(idx->ws.cnt.reserve(2 * sizeof(double)));
     VSC_TRY(launch_meta_looseness(idx->ref8m.as<float4>() + row0, real, idx->ws.cnt.as<double>(), idx->stream));
@@ -534,34 +533,25 @@ static int i8_quantise(vsc_index* idx, int64_t row0, int64_t rows, int64_t count
 // pointless) and either quantise just the new rows (set unchanged) or mark the whole image stale.
 static int i8_after_add(vsc_index* idx, int64_t first_new, int64_t n, int64_t need_rows) {
     const int dpad = idx->dpad;
-    VSC_TRY(idx->ws.tmp.reserve((size_t)2 * dpad * sizeof(unsigned)));
-    unsigned* d_mn = idx->ws.tmp.as<unsigned>();
+    VSC_TRY(idx->ws.sort.tmp.reserve((size_t)2 * dpad * sizeof(unsigned)));
+    unsigned* d_mn = idx->ws.sort.tmp.as<unsigned>();
     unsigned* d_mx = d_mn + dpad;
-    std::vector<unsigned> mn((size_t)dpad), mx((size_t)dpad);
-    if (sq16(idx)) {
-        // the decoded values, range by range; the ranges' keys are folded on the host
-        std::vector<unsigned> pmn((size_t)dpad), pmx((size_t)dpad);
-        std::fill(mn.begin(), mn.end(), 0xffffffffu);
-        std::fill(mx.begin(), mx.end(), 0u);
-        for (int64_t c0 = first_new; c0 < first_new + n; c0 += DEC_CHUNK_ROWS) {
-            const int64_t rc = std::min(DEC_CHUNK_ROWS, first_new + n - c0);
-            float* dec = nullptr;
-            VSC_TRY(decode_range(idx, c0, rc, &dec));
-            VSC_TRY(launch_dim_minmax(dec, rc, dpad, d_mn, d_mx, idx->stream));
-            VSC_HIP(hipMemcpyAsync(pmn.data(), d_mn, (size_t)dpad * sizeof(unsigned), hipMemcpyDeviceToHost, idx->stream));
-            VSC_HIP(hipMemcpyAsync(pmx.data(), d_mx, (size_t)dpad * sizeof(unsigned), hipMemcpyDeviceToHost, idx->stream));
-            VSC_HIP(hipStreamSynchronize(idx->stream));
+    // order-preserving keys of the per-coordinate min / max, range by range; the first range's keys are taken as they
+    // are, later ones folded in
+    std::vector<unsigned> mn((size_t)dpad), mx((size_t)dpad), pmn((size_t)dpad), pmx((size_t)dpad);
+    VSC_TRY(for_ref_ranges(idx, first_new, n, [&](const float* src, int64_t first, int64_t rows) -> int {
+        const bool head = first == first_new;
+        VSC_TRY(launch_dim_minmax(src, rows, dpad, d_mn, d_mx, idx->stream));
+        VSC_HIP(hipMemcpyAsync((head ? mn : pmn).data(), d_mn, (size_t)dpad * sizeof(unsigned), hipMemcpyDeviceToHost, idx->stream));
+        VSC_HIP(hipMemcpyAsync((head ? mx : pmx).data(), d_mx, (size_t)dpad * sizeof(unsigned), hipMemcpyDeviceToHost, idx->stream));
+        VSC_HIP(hipStreamSynchronize(idx->stream));
+        if (!head)
             for (int p = 0; p < dpad; ++p) {
                 mn[(size_t)p] = std::min(mn[(size_t)p], pmn[(size_t)p]);
                 mx[(size_t)p] = std::max(mx[(size_t)p], pmx[(size_t)p]);
             }
-        }
-    } else {
-    VSC_TRY(launch_dim_minmax(idx->ref.as<float>() + first_new * dpad, n, dpad, d_mn, d_mx, idx->stream));
-    VSC_HIP(hipMemcpyAsync(mn.data(), d_mn, (size_t)dpad * sizeof(unsigned), hipMemcpyDeviceToHost, idx->stream));
-    VSC_HIP(hipMemcpyAsync(mx.data(), d_mx, (size_t)dpad * sizeof(unsigned), hipMemcpyDeviceToHost, idx->stream));
-    VSC_HIP(hipStreamSynchronize(idx->stream));
-    }
+        return VSC_OK;
+    }));
     if (idx->cmin_key.empty()) {
         idx->cmin_key.assign((size_t)idx->dim, 0xffffffffu);
         idx->cmax_key.assign((size_t)idx->dim, 0u);

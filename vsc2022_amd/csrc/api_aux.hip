@@ -99,7 +99,7 @@ int vsc_pair_max(const int32_t* hit_i, const int32_t* hit_j, const float* hit_s,
     AuxTimer tm;
     tm.begin(0, c->stream);
     VSC_TRY(pair_max_device((const int32_t*)di, (const int32_t*)dj, (const float*)ds, n, (const int32_t*)dq,
-                            (const int32_t*)dr, nq_rows, nr_rows, ws.w0, ws.w1, ws.w2, ws.w3, ws.tmp, ws.cnt, oq, orr, os, of,
+                            (const int32_t*)dr, nq_rows, nr_rows, ws.sort, ws.cnt, oq, orr, os, of,
                             ocap, &np, c->stream));
     tm.end(12.0 * (double)n + 20.0 * (double)np, c->stream);  // hits in, (q, r, score, first hit) per pair out
     *n_pairs = np;
@@ -148,8 +148,8 @@ int vsc_sort_hits(const int32_t* hit_i, const int32_t* hit_j, const float* hit_s
     }
     const int64_t all = (int64_t)1 << 31;
     int64_t m = 0;
-    VSC_TRY(sort_hits_topk((const int32_t*)di, (const int32_t*)dj, (const float*)ds, n, n, max_row > 0 ? max_row : all,
-                           max_ref > 0 ? max_ref : all, ws.w0, ws.w1, ws.w2, ws.w3, ws.tmp, oi, oj, os, 0, &m, c->stream));
+    VSC_TRY(sort_hits_topk({(const int32_t*)di, (const int32_t*)dj, (const float*)ds}, n, n, max_row > 0 ? max_row : all,
+                           max_ref > 0 ? max_ref : all, ws.sort, {oi, oj, os}, 0, &m, c->stream));
     if (out_mem == VSC_MEM_HOST) {
         VSC_HIP(hipMemcpyAsync(out_i, oi, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
         VSC_HIP(hipMemcpyAsync(out_j, oj, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
@@ -216,7 +216,7 @@ int vsc_filter_hits(const int32_t* hit_i, const int32_t* hit_j, const float* hit
     }
     std::lock_guard<std::mutex> lk(c->mu);
     VSC_TRY(c->ws.cnt.reserve(sizeof(unsigned long long)));
-    VSC_TRY(launch_filter_hits(hit_i, hit_j, hit_s, (long long)n, radius, out_i, out_j, out_s, c->ws.cnt.as<unsigned long long>(),
+    VSC_TRY(launch_filter_hits({hit_i, hit_j, hit_s}, (long long)n, radius, {out_i, out_j, out_s}, c->ws.cnt.as<unsigned long long>(),
                                c->stream));
     unsigned long long kept = 0;
     VSC_HIP(hipMemcpyAsync(&kept, c->ws.cnt.p, sizeof(kept), hipMemcpyDeviceToHost, c->stream));
@@ -243,7 +243,7 @@ int vsc_argsort_scores(const float* scores, int64_t n, int mem, int32_t* perm, i
     const void* ds;
     VSC_TRY(to_device(scores, (size_t)n * 4, mem, ws.hA[2], &ds, c->stream));
     const int32_t* p = nullptr;
-    VSC_TRY(argsort_scores_desc((const float*)ds, n, ws.w0, ws.w1, ws.w2, ws.w3, ws.tmp, &p, c->stream));
+    VSC_TRY(argsort_scores_desc((const float*)ds, n, ws.sort, &p, c->stream));
     VSC_HIP(hipMemcpyAsync(perm, p, (size_t)n * 4, perm_mem == VSC_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
                            c->stream));
     VSC_HIP(hipStreamSynchronize(c->stream));
@@ -615,16 +615,16 @@ int vsc_tn_forward_sim(const float* sims, const int64_t* sims_off, const int32_t
     Workspace& ws = c->ws;
     const int64_t total = sims_off[n_pairs];
     VSC_TRY(ws.mat.reserve((size_t)std::max<int64_t>(total, 1) * 4));
-    VSC_TRY(ws.w0.reserve((size_t)(n_pairs + 1) * 8));
-    VSC_TRY(ws.w2.reserve((size_t)n_pairs * 4));
-    VSC_TRY(ws.w3.reserve((size_t)n_pairs * 4));
+    VSC_TRY(ws.sort.w0.reserve((size_t)(n_pairs + 1) * 8));
+    VSC_TRY(ws.sort.w2.reserve((size_t)n_pairs * 4));
+    VSC_TRY(ws.sort.w3.reserve((size_t)n_pairs * 4));
     VSC_TRY(ws.out[0].reserve((size_t)n_pairs * 4));
     VSC_TRY(ws.out[1].reserve((size_t)n_pairs * VSC_TN_MAX_BOXES * 16));
     VSC_TRY(ws.out[2].reserve((size_t)n_pairs * VSC_TN_MAX_BOXES * 4));
     if (total) VSC_HIP(hipMemcpyAsync(ws.mat.p, sims, (size_t)total * 4, hipMemcpyHostToDevice, c->stream));
-    VSC_HIP(hipMemcpyAsync(ws.w0.p, sims_off, (size_t)(n_pairs + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    VSC_HIP(hipMemcpyAsync(ws.w2.p, lq, (size_t)n_pairs * 4, hipMemcpyHostToDevice, c->stream));
-    VSC_HIP(hipMemcpyAsync(ws.w3.p, lr, (size_t)n_pairs * 4, hipMemcpyHostToDevice, c->stream));
+    VSC_HIP(hipMemcpyAsync(ws.sort.w0.p, sims_off, (size_t)(n_pairs + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    VSC_HIP(hipMemcpyAsync(ws.sort.w2.p, lq, (size_t)n_pairs * 4, hipMemcpyHostToDevice, c->stream));
+    VSC_HIP(hipMemcpyAsync(ws.sort.w3.p, lr, (size_t)n_pairs * 4, hipMemcpyHostToDevice, c->stream));
     TnPairArgs base;
     memset(&base, 0, sizeof(base));
     base.prm = *params;
@@ -633,9 +633,9 @@ int vsc_tn_forward_sim(const float* sims, const int64_t* sims_off, const int32_t
     base.out_boxes = ws.out[1].as<int32_t>();
     base.out_boxmax = ws.out[2].as<float>();
     base.sims_in = ws.mat.as<float>();
-    base.sims_off = ws.w0.as<int64_t>();
-    base.sims_lq = ws.w2.as<int32_t>();
-    base.sims_lr = ws.w3.as<int32_t>();
+    base.sims_off = ws.sort.w0.as<int64_t>();
+    base.sims_lq = ws.sort.w2.as<int32_t>();
+    base.sims_lr = ws.sort.w3.as<int32_t>();
     std::vector<int32_t> lqs(lq, lq + n_pairs), lrs(lr, lr + n_pairs);
     VSC_TRY(tn_run_buckets(base, lqs, lrs, ws.maps0, ws.maps1, c->stream));
     VSC_HIP(hipMemcpyAsync(out_nbox, ws.out[0].p, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, c->stream));

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -22,7 +23,8 @@ struct Workspace {
     DevBuf qbuf;    // packed query rows
     DevBuf hA[3], hB[3];  // kept hits (i, j, s) + compaction target
     DevBuf ctl;     // SelectCtl
-    DevBuf w0, w1, w2, w3, tmp, cnt;  // sort scratch
+    SortScratch sort;  // scratch of the radix sorts (sortpairs.hip)
+    DevBuf cnt;        // small counters read back by the host
     DevBuf out[4];  // device-side outputs when the caller wants host results
     DevBuf parts, partj, mat, maps0, maps1;
     DevBuf qh, qn;  // fp16 image + norm bounds of the query rows (pre-filter)
@@ -41,6 +43,9 @@ struct Workspace {
     // a range, and the per-range partial lists of the exact k-NN
     DevBuf dec, flag, kparts, kpartj;
     DevBuf sample, sk[3], tk[3];  // proven top-K route (api_search.hip): the row sample, its sorted hits, the K + 1 best of the steady run
+    HitView hits_a() const { return {hA[0].as<int32_t>(), hA[1].as<int32_t>(), hA[2].as<float>()}; }
+    HitView hits_b() const { return {hB[0].as<int32_t>(), hB[1].as<int32_t>(), hB[2].as<float>()}; }
+    HitView hits_out() const { return {out[0].as<int32_t>(), out[1].as<int32_t>(), out[2].as<float>()}; }
     void release() {
         stage.release(); qbuf.release(); sample.release();
         dec.release(); flag.release(); kparts.release(); kpartj.release();
@@ -52,7 +57,7 @@ struct Workspace {
         cstmp.release(); csn.release();
         for (auto& b : hA) b.release();
         for (auto& b : hB) b.release();
-        ctl.release(); w0.release(); w1.release(); w2.release(); w3.release(); tmp.release(); cnt.release();
+        ctl.release(); sort.release(); cnt.release();
         for (auto& b : out) b.release();
         parts.release(); partj.release(); mat.release(); maps0.release(); maps1.release();
     }
@@ -225,6 +230,12 @@ struct AuxTimer {
 constexpr int64_t DEC_CHUNK_ROWS = 65536;
 inline bool sq16(const vsc_index* idx) { return idx->codec == VSC_CODEC_SQFP16; }
 int decode_range(vsc_index* idx, int64_t r0, int64_t rows, float** out);
+// The one walk over the reference rows [r0, r0 + rows) as packed fp32 (api.hip).  Flat: ONE call of fn, with the rows
+// where they lie; SQfp16: one call per decoded range of <= DEC_CHUNK_ROWS rows.  The ranges share ws.dec: what fn
+// enqueues for a range is ordered before the next range's decode by the stream.
+using RefRangeFn = std::function<int(const float* packed_rows, int64_t first_row, int64_t n_rows)>;
+int for_ref_ranges(vsc_index* idx, int64_t r0, int64_t rows, const RefRangeFn& fn);
+int ref_range_count(const vsc_index* idx, int64_t r0, int64_t rows);  // calls of fn that walk makes
 
 // index upkeep (api.hip)
 int i8_prepare(vsc_index* idx);         // before a search that may use the int8 kernel: bring the image up to date

@@ -25,45 +25,36 @@ static int knn_exact_ip(vsc_index* idx, const float* qp, int64_t nq, int64_t nr,
     nchunk = std::min(nchunk, 64);
     if (idx->knn_nchunk > 0) nchunk = std::max(1, std::min(std::min(idx->knn_nchunk, tr), 64));
     const int64_t nq_pad = (int64_t)tq * 128;
+    // The kernel streams whole packed rows, one range of them per launch (for_ref_ranges).  A single range hands its partial lists straight to the merge.  With several, every range's lists (refs
+    // relative to it) go to their slot among the lists of all ranges, which the merge treats like the runs of one
+    // launch -- the same (score desc, ref asc) order, the same scores.
+    const int nranges = ref_range_count(idx, 0, nr);
+    int rg = 0;  // ordinal of the range the walk is at
     VSC_TRY(idx->ws.parts.reserve((size_t)nq_pad * nchunk * k * 4));
     VSC_TRY(idx->ws.partj.reserve((size_t)nq_pad * nchunk * k * 4));
-    SimKnnArgs a{qp, idx->ref.as<float>(), idx->dpad, (int)nq, (int)nr, tq, tr, nchunk, k,
-                 idx->ws.parts.as<float>(), idx->ws.partj.as<int32_t>(), idx->knn_first_tile ? 0 : 1};
-    hipEvent_t stop;
-    if (sq16(idx)) {
-        // the kernel streams whole packed rows: bounded ranges of the store are decoded for it; a range's partial
-        // lists (refs relative to it) go to their slot among the lists of all ranges, which the merge below treats
-        // like the runs of one launch -- the same (score desc, ref asc) order, the same scores
-        const int nranges = (int)((nr + DEC_CHUNK_ROWS - 1) / DEC_CHUNK_ROWS);
-        const int nch = std::max(1, std::min(nchunk, (int)((std::min(nr, DEC_CHUNK_ROWS) + 127) / 128)));
-        VSC_TRY(idx->ws.kparts.reserve((size_t)nq_pad * nranges * nch * k * 4));
-        VSC_TRY(idx->ws.kpartj.reserve((size_t)nq_pad * nranges * nch * k * 4));
-        VSC_TRY(idx->ws.parts.reserve((size_t)nq_pad * nch * k * 4));
-        VSC_TRY(idx->ws.partj.reserve((size_t)nq_pad * nch * k * 4));
-        for (int rg = 0; rg < nranges; ++rg) {
-            const int64_t j0 = (int64_t)rg * DEC_CHUNK_ROWS, rows = std::min(DEC_CHUNK_ROWS, nr - j0);
-            float* dec = nullptr;
-            VSC_TRY(decode_range(idx, j0, rows, &dec));
-            a.R = dec;
-            a.nr = (int)rows;
-            a.tr = (int)((rows + 127) / 128);
-            a.nchunk = nch;
-            VSC_TRY(prof_begin(idx, &stop));
-            VSC_TRY(launch_sim_knn(a, idx->stream));
-            VSC_TRY(prof_end(idx, stop, 2.0 * (double)nq * (double)rows * (double)idx->dim));
-            VSC_TRY(launch_knn_parts_scatter(a.part_s, a.part_j, nq_pad, nch, k, rg, nranges, (int)j0, idx->ws.kparts.as<float>(),
-                                             idx->ws.kpartj.as<int32_t>(), idx->stream));
-        }
-        KnnMergeArgs m{idx->ws.kparts.as<float>(), idx->ws.kpartj.as<int32_t>(), (int)nq, nranges * nch, k, ds, dj, 0};
-        VSC_TRY(launch_knn_merge(m, idx->stream));
-        return VSC_OK;
+    if (nranges > 1) {
+        VSC_TRY(idx->ws.kparts.reserve((size_t)nq_pad * nranges * nchunk * k * 4));
+        VSC_TRY(idx->ws.kpartj.reserve((size_t)nq_pad * nranges * nchunk * k * 4));
     }
-    VSC_TRY(prof_begin(idx, &stop));
-    VSC_TRY(launch_sim_knn(a, idx->stream));
-    VSC_TRY(prof_end(idx, stop, 2.0 * (double)nq * (double)nr * (double)idx->dim));
-    KnnMergeArgs m{idx->ws.parts.as<float>(), idx->ws.partj.as<int32_t>(), (int)nq, nchunk, k, ds, dj, 0};
-    VSC_TRY(launch_knn_merge(m, idx->stream));
-    return VSC_OK;
+    SimKnnArgs a{qp, nullptr, idx->dpad, (int)nq, 0, tq, 0, nchunk, k,
+                 idx->ws.parts.as<float>(), idx->ws.partj.as<int32_t>(), idx->knn_first_tile ? 0 : 1};
+    VSC_TRY(for_ref_ranges(idx, 0, nr, [&](const float* rows, int64_t j0, int64_t n) -> int {
+        a.R = rows;
+        a.nr = (int)n;
+        a.tr = (int)((n + 127) / 128);
+        hipEvent_t stop;
+        VSC_TRY(prof_begin(idx, &stop));
+        VSC_TRY(launch_sim_knn(a, idx->stream));
+        VSC_TRY(prof_end(idx, stop, 2.0 * (double)nq * (double)n * (double)idx->dim));
+        if (nranges > 1)
+            VSC_TRY(launch_knn_parts_scatter(a.part_s, a.part_j, nq_pad, nchunk, k, rg, nranges, (int)j0,
+                                             idx->ws.kparts.as<float>(), idx->ws.kpartj.as<int32_t>(), idx->stream));
+        ++rg;
+        return VSC_OK;
+    }));
+    KnnMergeArgs m{nranges > 1 ? idx->ws.kparts.as<float>() : a.part_s, nranges > 1 ? idx->ws.kpartj.as<int32_t>() : a.part_j,
+                   (int)nq, nranges * nchunk, k, ds, dj, 0};
+    return launch_knn_merge(m, idx->stream);
 }
 
 // One thresholded pass of the pre-filtered k-NN over the reference rows [r_begin, r_end): pre-filter + exact stage of
@@ -107,8 +98,7 @@ static int knn_threshold_pass(vsc_index* idx, const float* qp, int64_t nq, int64
     VSC_TRY(init_ctl(idx, 0.0f));
     SelectCtl* ctl = idx->ws.ctl.as<SelectCtl>();
     if (r_begin > 0)
-        VSC_TRY(launch_knn_seed_hits(ds, dj, nq, k, idx->ws.hA[0].as<int32_t>(), idx->ws.hA[1].as<int32_t>(),
-                                     idx->ws.hA[2].as<float>(), &ctl->n, idx->stream));
+        VSC_TRY(launch_knn_seed_hits(ds, dj, nq, k, idx->ws.hits_a(), &ctl->n, idx->stream));
     for (int64_t i0 = 0; i0 < nq; i0 += step)
         VSC_TRY(enqueue_f16(idx, qp, i0, std::min(nq, i0 + step), cap, idx->ws.rowthr.as<float>(), ccap, r_end, use_i8, r_begin));
     SelectCtl h;
@@ -116,9 +106,7 @@ static int knn_threshold_pass(vsc_index* idx, const float* qp, int64_t nq, int64
     VSC_HIP(hipStreamSynchronize(idx->stream));
     idx->stat_candidates += h.n_cand_total;  // (over the ranges of one k-NN: knn_prefiltered resets it)
     if (h.overflow) return VSC_ERR_OVERFLOW;
-    VSC_TRY(knn_from_hits(idx->ws.hA[0].as<int32_t>(), idx->ws.hA[1].as<int32_t>(), idx->ws.hA[2].as<float>(),
-                          (int64_t)h.n, nq, k, idx->ws.w0, idx->ws.w1, idx->ws.w2, idx->ws.w3, idx->ws.tmp, ds, dj,
-                          idx->stream));
+    VSC_TRY(knn_from_hits(idx->ws.hits_a(), (int64_t)h.n, nq, k, idx->ws.sort, ds, dj, idx->stream));
     return VSC_OK;
 }
 

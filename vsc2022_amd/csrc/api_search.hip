@@ -3,36 +3,298 @@
 // (pre-filter launch + candidate list + exact stage) that the k-NN's threshold passes share (api_knn.hip).
 #include "api_internal.h"
 
-// The candidate list of one pre-filter launch (cand_list.h): `ccap` entries in per-wave segments + the chunked tail
-// behind them.  Fills the list fields that SimF16Args / SimF16PArgs / SimI8PArgs share and keeps the geometry for
-// the exact stage.
-struct CandList {
-    int grid = 0, seg_cap = 0, tail_shift = 6;
-    int64_t tail_base = 0;
-    long long tail_cap = 0;
+// One pre-filtered batch as its steps see it: query rows [i0, i0 + nq) of the packed image against the reference rows
+// [nr_begin, nr_end); row_thr = the k-NN's per-row thresholds (indexed by absolute row), nullptr = the search radius.
+struct F16Batch {
+    const float* qpacked;
+    int64_t i0;
+    int nq;
+    const float* row_thr;
+    int64_t nr_begin, nr_end;
+    int64_t nrefs() const { return nr_end - nr_begin; }  // rows the kernels see
 };
-template <class Args>
-static int cand_list_setup(vsc_index* idx, int64_t ccap, int grid, Args& f, CandList& cl) {
+
+// |fp16 score - exact score| <= c1 |q||r| + c2 (|q| + |r|) + c3   (|x| = L2 norm):
+//   rounding to fp16: |x - h(x)| <= 2^-11 |x| + 2^-25 per element (normal / subnormal range)
+//     => sum |q r - h(q) h(r)| <= (2^-10 + 2^-22) |q||r| + 2^-25 * 1.001 * sqrt(D) (|q|+|r|) + D 2^-50
+//   accumulation: the exact fp32 fma chain (D roundings) and the MFMA's fp32 accumulation
+//     (D/16 instructions of 16 products + addend) each stay within 2^-23 |q||r| per operation
+struct F16Bound { float c1, c2, c3; };
+static F16Bound f16_bound(int dpadh) {
+    const double D = (double)dpadh;
+    return {(float)(ldexp(1.0, -10) + ldexp(1.0, -22) + (2.0 * D + D / 16.0 + 16.0) * ldexp(1.0, -23)),
+            (float)(ldexp(1.0, -25) * 1.001 * sqrt(D)), (float)(D * ldexp(1.0, -50))};
+}
+
+// The candidate list of one pre-filter launch of `grid` workgroups (cand_list.h): `ccap` entries in per-wave segments +
+// the chunked tail behind them, in the workspace's arrays.  The same block goes to the launch and to the exact stage.
+static int cand_list_plan(vsc_index* idx, int64_t ccap, int grid, CandList& l) {
     SelectCtl* ctl = idx->ws.ctl.as<SelectCtl>();
-    cl.grid = grid;
-    cl.seg_cap = (int)std::min<int64_t>(ccap / (grid * 8), 0x7fffffff);
-    cl.tail_base = (int64_t)cl.seg_cap * grid * 8;
-    cl.tail_cap = cand_entries(ccap) - cl.tail_base;
-    cl.tail_shift = tail_chunk_shift_for(cl.tail_cap, grid * 8);
-    VSC_TRY(idx->ws.tailfill.reserve((size_t)((cl.tail_cap >> cl.tail_shift) + 2) * sizeof(int)));
-    f.out_i = idx->ws.ci.as<int32_t>();
-    f.out_j = idx->ws.cj.as<int32_t>();
-    f.seg_cap = cl.seg_cap;
-    f.seg_count = idx->ws.segcnt.as<int>();
-    f.tail_base = cl.tail_base;
-    f.tail_cap = cl.tail_cap;
-    f.tail_shift = cl.tail_shift;
-    f.tail_fill = idx->ws.tailfill.as<int>();
-    f.tail_count = &ctl->n_tail;
-    f.overflow = &ctl->overflow;
+    l.i = idx->ws.ci.as<int32_t>();
+    l.j = idx->ws.cj.as<int32_t>();
+    l.n_seg = grid * 8;
+    l.seg_cap = (int)std::min<int64_t>(ccap / l.n_seg, 0x7fffffff);
+    l.seg_count = idx->ws.segcnt.as<int>();
+    l.tail_base = (int64_t)l.seg_cap * l.n_seg;
+    l.tail_cap = cand_entries(ccap) - l.tail_base;
+    l.tail_shift = tail_chunk_shift_for(l.tail_cap, l.n_seg);
+    VSC_TRY(idx->ws.tailfill.reserve((size_t)((l.tail_cap >> l.tail_shift) + 2) * sizeof(int)));
+    l.tail_fill = idx->ws.tailfill.as<int>();
+    l.tail_count = &ctl->n_tail;
+    l.overflow = &ctl->overflow;
     return VSC_OK;
 }
 
+// The three pre-filter launches.  Each fills its kernel's arg block, plans the candidate list `cl` for its grid and
+// opens its profiling bracket right before the launch (`stop`; enqueue_f16 closes it).
+
+// dims > 512: 256x256 LDS-ring kernel (sim_f16.hip) on the natural image
+static int prefilter_f16_ring(vsc_index* idx, const F16Batch& b, int64_t ccap, const F16Bound& fb, CandList& cl, hipEvent_t* stop) {
+    SimF16Args f;
+    f.Q = idx->ws.qh.as<_Float16>() + b.i0 * idx->dpadh;
+    f.R = idx->refh.as<_Float16>() + b.nr_begin * idx->dpadh;
+    f.qn = idx->ws.qn.as<float>() + b.i0;
+    f.rn = idx->refn.as<float>() + b.nr_begin;
+    f.dpadh = idx->dpadh;
+    f.nq = b.nq;
+    f.i0 = (int)b.i0;
+    f.nr = (int)b.nrefs();
+    f.tq = (b.nq + 255) / 256;
+    f.tr = (int)((b.nrefs() + 255) / 256);
+    f.c1 = fb.c1; f.c2 = fb.c2; f.c3 = fb.c3;
+    f.radius = &idx->ws.ctl.as<SelectCtl>()->radius;
+    f.row_thr = b.row_thr ? b.row_thr + b.i0 : nullptr;
+    VSC_TRY(cand_list_plan(idx, ccap, sim_f16_grid(f.tq, f.tr), cl));
+    f.list = cl;
+    VSC_TRY(prof_begin(idx, stop, 1));
+    return launch_sim_f16(f, idx->stream);
+}
+
+// panel-stationary kernel (sim_f16p.hip): LDS-resident query panels x the fragment-major reference image
+static int prefilter_f16_panel(vsc_index* idx, const F16Batch& b, int64_t ccap, const F16Bound& fb, CandList& cl, hipEvent_t* stop) {
+    SimF16PArgs f;
+    int grid = 0;
+    sim_f16p_plan(b.nq, b.nrefs(), &f.npanel, &f.nsteps, &f.slice, &grid);
+    VSC_TRY(idx->ws.slices.reserve((size_t)f.npanel * sizeof(int)));
+    f.Q = idx->ws.qh.as<_Float16>() + b.i0 * idx->dpadh;
+    f.Rf = static_cast<const char*>(idx->refh.p) + b.nr_begin * idx->dpadh * 2;
+    f.qn = idx->ws.qn.as<float>() + b.i0;
+    f.rn = idx->refn.as<float>() + b.nr_begin;
+    f.dpadh = idx->dpadh;
+    f.nq = b.nq;
+    f.i0 = (int)b.i0;
+    f.nr = (int)b.nrefs();
+    f.next_slice = idx->ws.slices.as<int>();
+    f.c1 = fb.c1; f.c2 = fb.c2; f.c3 = fb.c3;
+    f.radius = &idx->ws.ctl.as<SelectCtl>()->radius;
+    f.row_thr = b.row_thr ? b.row_thr + b.i0 : nullptr;
+    VSC_TRY(cand_list_plan(idx, ccap, grid, cl));
+    f.list = cl;
+    VSC_TRY(prof_begin(idx, stop, 1));
+    return launch_sim_f16p(f, grid, idx->stream);
+}
+
+// The int8 launch's preamble: the rows' thresholds with what the images leave out folded in, the order the launch sees
+// its rows in, and the launch's own int8 image (`npanel_q` panels, one scale per 128-row panel).  Returns `perm`
+// (perm[position] = row; nullptr: the rows' own order) and `rt_pos`, the thresholds in position order (nullptr: the
+// search radius for all rows).
+static int i8_preamble(vsc_index* idx, const F16Batch& b, int npanel_q, const int32_t** perm_out, float** rt_pos_out) {
+    SelectCtl* ctl = idx->ws.ctl.as<SelectCtl>();
+    Workspace& ws = idx->ws;
+    const float* q = b.qpacked + b.i0 * idx->dpad;
+    const int nqb = b.nq;
+    const int32_t* perm = nullptr;
+    float* rt_pos = nullptr;
+    const float* thr_src = b.row_thr ? b.row_thr + b.i0 : nullptr;
+    if (idx->i8_ex.n > 0 || idx->i8_mu_on) {
+        // coordinates the images leave out (all references agree on them) act through the rows' thresholds:
+        // t_row - sum_c q_c v_c, with t_row the row's k-NN threshold or the search radius; a centred reference
+        // image (quant_i8.hip) adds the rows' x . mu the same way
+        VSC_TRY(ws.rt8b.reserve((size_t)nqb * sizeof(float)));
+        const float *cen = nullptr, *cmag = nullptr;
+        if (idx->i8_mu_on) {
+            VSC_TRY(ws.rt8d.reserve((size_t)2 * nqb * sizeof(float)));
+            VSC_TRY(launch_row_center(q, idx->dpad, nqb, idx->i8_mu.as<float>(), ws.rt8d.as<float>(), ws.rt8d.as<float>() + nqb,
+                                      idx->stream));
+            cen = ws.rt8d.as<float>();
+            cmag = cen + nqb;
+        }
+        VSC_TRY(launch_row_bias_thresholds(q, idx->dpad, nqb, thr_src, &ctl->radius, idx->i8_ex, cen, cmag, ws.rt8b.as<float>(),
+                                           idx->stream));
+        thr_src = ws.rt8b.as<float>();
+    }
+    // VSC_I8_SORT=0: rows in their own order (A/B; the kernel then gates blocks of unrelated thresholds)
+    const bool sort_rows = idx->i8_sort_rows;
+    if (thr_src) {
+        VSC_TRY(ws.rt8.reserve((size_t)npanel_q * F16P_PANEL_ROWS * sizeof(float)));
+        rt_pos = ws.rt8.as<float>();
+    }
+    if (thr_src && sort_rows) {
+        // thresholds that differ from row to row: the launch sees its rows sorted by threshold (the kernel
+        // gates a tile by its panel's smallest threshold and a 16-row block by the block's)
+        if (idx->i8_group_shift > 0 && !b.row_thr && nqb >= (4 << idx->i8_group_shift)) {
+            // ... and, inside groups of 512 positions of that order, by the rows' largest element (sortpairs.hip).
+            // Only for the radius search over excluded coordinates (thresholds = radius - the rows' bias: a
+            // narrow spread): configs[3] 1162 -> 1086 M candidates, exact stage 367 -> 341 ms (groups of 256 /
+            // 512 / 1024 / 2048 / 4096: 1110 / 1086 / 1090 / 1125 / 1205 M).  The k-NN's thresholds -- each
+            // row's best score so far -- spread far more: there the same grouping cost 2 % (892 -> 907 ms).
+            VSC_TRY(ws.rt8c.reserve((size_t)nqb * sizeof(float)));
+            VSC_TRY(launch_row_absmax(q, idx->dpad, nqb, idx->i8_ex, ws.rt8c.as<float>(), idx->stream));
+            VSC_TRY(sort_rows_by_threshold_then_scale(thr_src, ws.rt8c.as<float>(), nqb, idx->i8_group_shift, ws.sort, &perm,
+                                                      idx->stream));
+        } else {
+            VSC_TRY(sort_rows_by_threshold(thr_src, nqb, ws.sort, &perm, idx->stream));
+        }
+    } else if (!thr_src && sort_rows && nqb >= 2 * F16P_PANEL_ROWS) {
+        // one threshold for all rows (the search radius): sort by the rows' largest element instead, so that
+        // a panel's shared scale is close to what each of its rows would have chosen (VSC_I8_SORT=0: off)
+        VSC_TRY(ws.rt8b.reserve((size_t)nqb * sizeof(float)));
+        VSC_TRY(launch_row_absmax(q, idx->dpad, nqb, idx->i8_ex, ws.rt8b.as<float>(), idx->stream));
+        VSC_TRY(sort_rows_by_threshold(ws.rt8b.as<float>(), nqb, ws.sort, &perm, idx->stream));
+    }
+    VSC_TRY(launch_quant_query_panels(q, idx->dpad, nqb, npanel_q, ws.q8.p, idx->dpad8, ws.pstat.as<float4>(), perm, thr_src,
+                                      rt_pos, idx->i8_ex, idx->stream));
+    *perm_out = perm;
+    *rt_pos_out = rt_pos;
+    return VSC_OK;
+}
+
+// int8 panel kernel (sim_i8p.hip): this launch's rows are quantised first, one scale per 128-row panel.  `perm` is set
+// when the candidate list will hold positions of a permuted launch.
+static int prefilter_i8(vsc_index* idx, const F16Batch& b, int64_t ccap, CandList& cl, const int32_t** perm, hipEvent_t* stop) {
+    SimI8PArgs f;
+    int grid = 0;
+    sim_f16p_plan(b.nq, b.nrefs(), &f.npanel, &f.nsteps, &f.slice, &grid);
+    {
+        // work order: slice-major items.  r03 (32x32x32 kernel): items of 16 col-steps (4 MiB of the int8 image at
+        // 512-d: what an XCD's L2 holds) +3 % on the bench over panel-major (2431 -> 2507-2515 TOP/s).  r04
+        // (16x16x64 kernel, configs[3]): 8 / 16 / 32 / 64 col-steps 2456 / 2390 / 2363 / 2368 ms per query set
+        // -- the faster K loop makes the hand-over (panel load + two barriers) the larger share: 32.
+        // VSC_I8P_ORDER=0: panel-major with stealing as in sim_f16p
+        const int slice_env = idx->i8p_slice;
+        f.order = idx->i8p_order;
+        if (f.order == 1) f.slice = std::max(1, std::min(f.nsteps, slice_env > 0 ? slice_env : 32));
+        else if (slice_env > 0) f.slice = std::max(1, std::min(f.nsteps, slice_env));
+    }
+    // work items of two panels (wave tiles of 256 rows x 32 columns: half the reference bytes per MFMA) where the
+    // launch is large enough; the quantised image then holds an even number of panels.  VSC_I8P_PAIR=0: off
+    f.pair = idx->i8p_pair && sim_i8p_pairs(idx->dpad8, f.npanel, f.nsteps, f.slice, idx->i8p_pair == 2) ? 1 : 0;
+    const int npanel_q = f.pair ? (f.npanel + 1) & ~1 : f.npanel;
+    VSC_TRY(idx->ws.slices.reserve(((size_t)f.npanel + 1) * sizeof(int)));
+    VSC_TRY(idx->ws.q8.reserve((size_t)npanel_q * F16P_PANEL_ROWS * idx->dpad8));
+    VSC_TRY(idx->ws.pstat.reserve((size_t)npanel_q * sizeof(float4)));
+    hipEvent_t prep_stop;
+    VSC_TRY(prof_begin(idx, &prep_stop, 6));
+    float* rt_pos = nullptr;
+    VSC_TRY(i8_preamble(idx, b, npanel_q, perm, &rt_pos));
+    f.Q = idx->ws.q8.p;
+    f.pstat = idx->ws.pstat.as<float4>();
+    f.Rf = static_cast<const char*>(idx->ref8.p) + b.nr_begin * idx->dpad8;  // (whole 64-row tiles: dpad8 x 64 B each)
+    f.rmeta = idx->ref8m.as<float4>() + b.nr_begin;
+    f.dpad8 = idx->dpad8;
+    f.nq = b.nq;
+    f.i0 = (int)b.i0;
+    f.nr = (int)b.nrefs();
+    f.next_slice = idx->ws.slices.as<int>();
+    // the exact fp32 chain is within dpad 2^-24 |q||r| (1 + tiny) of the real inner product
+    f.c_acc = (float)(((double)idx->dpad + 2.0) * ldexp(1.0, -23));
+    f.radius = &idx->ws.ctl.as<SelectCtl>()->radius;
+    f.row_thr = rt_pos;
+    VSC_TRY(cand_list_plan(idx, ccap, grid, cl));
+    f.list = cl;
+    VSC_TRY(prof_end(idx, prep_stop, 0.0, 6));
+    VSC_TRY(prof_begin(idx, stop, 5));  // (the kernel alone: what the roofline figure is about)
+    return launch_sim_i8p(f, grid, idx->stream);
+}
+
+// Exact scores of a launch's candidates `cl`; those above the radius (at or above the row's threshold) join the kept
+// hits, at most `cap` of them.  `perm`: the list holds positions of a permuted int8 launch; `from_i8`: the candidates
+// may pass the fp16 screen first.
+static int exact_stage(vsc_index* idx, const F16Batch& b, int64_t cap, const CandList& cl, const int32_t* perm,
+                       const F16Bound& fb, bool from_i8) {
+    SelectCtl* ctl = idx->ws.ctl.as<SelectCtl>();
+    Workspace& ws = idx->ws;
+    const HitView kept = ws.hits_a();
+    RescoreArgs r;
+    r.Q = b.qpacked;
+    r.R = idx->ref.as<float>();
+    r.dpad = idx->dpad;
+    r.list = cl;
+    r.perm = perm;
+    r.perm_i0 = (int)b.i0;
+    r.n_cand_total = &ctl->n_cand_total;
+    r.radius = &ctl->radius;
+    r.out_i = kept.i;
+    r.out_j = kept.j;
+    r.out_s = kept.s;
+    r.counter = &ctl->n;
+    r.cap = cap;
+    r.row_thr = b.row_thr;
+    r.j0 = (int)b.nr_begin;
+    if (sq16(idx)) {  // the reference rows come from the fp16 store (sim_f16.hip: rescore_list<SRC>)
+        r.R = nullptr;
+        r.Rh = idx->refh.as<_Float16>();
+        r.dpadh = idx->dpadh;
+        r.rsrc = idx->frag ? 2 : 1;
+    }
+    // The candidates are compacted out of the waves' segments, sorted by reference row and re-scored as one dense
+    // list (sim_f16.hip, "candidates ordered by reference row"): 74 -> 54 ms per bench step, k-NN k = 20 140 ->
+    // 100 ms.  It needs the candidate count on the host (buffer sizes, grid of the sort): one stream sync per
+    // launch, ~20 us against launches of 3-30 ms.  VSC_RESCORE_SORT=0: the segments as they are.
+    if (!idx->rescore_by_ref) return launch_rescore(r, idx->stream);
+    // count first (one tiny kernel + the stream sync the sort needs anyway), then size the four dense lists of
+    // the sort from what the launch really left behind -- not from the list's capacity (96 bytes
+    // per unit of capacity, 26 GB for a default range search whose launches hold a few percent of that)
+    VSC_TRY(ws.csn.reserve(3 * sizeof(unsigned long long)));
+    unsigned long long* csn = ws.csn.as<unsigned long long>();
+    const int n_chunks_max = (int)std::min<long long>((cl.tail_cap >> cl.tail_shift) + 1, 1 << 20);
+    VSC_TRY(launch_cand_count(r, n_chunks_max, csn + 2, idx->stream));
+    unsigned long long n_c = 0;
+    VSC_HIP(hipMemcpyAsync(&n_c, csn + 2, sizeof(n_c), hipMemcpyDeviceToHost, idx->stream));
+    VSC_HIP(hipStreamSynchronize(idx->stream));
+    // (grown in steps of a quarter so that launches of slowly varying size do not reallocate every time)
+    const size_t cap_e = (size_t)(n_c + n_c / 4 + 4096);
+    for (auto& buf : ws.cs)
+        if (buf.bytes < (size_t)(n_c + 1) * sizeof(uint32_t)) VSC_TRY(buf.reserve(cap_e * sizeof(uint32_t)));
+    uint32_t* cs[4] = {ws.cs[0].as<uint32_t>(), ws.cs[1].as<uint32_t>(), ws.cs[2].as<uint32_t>(), ws.cs[3].as<uint32_t>()};
+    VSC_TRY(launch_cand_compact(r, n_chunks_max, cs[0], cs[2], csn, idx->stream));
+    const uint32_t *sj = nullptr, *si = nullptr;
+    VSC_TRY(sort_candidates_by_ref(cs[0], cs[1], cs[2], cs[3], (int64_t)n_c, b.nr_end, ws.cstmp, &sj, &si, idx->stream));
+    // VSC_I8_SCREEN=1: int8 launches pass an fp16 screen first (sim_f16.hip: f16_screen_kernel).  Measured
+    // neutral and therefore OFF by default: 29 % of the int8 candidates survive it (bench, 128 M -> 37 M per
+    // step), the screen moves half the bytes per pair (23.8 ms) and the exact stage then costs 35.6 instead of
+    // 59.8 ms -- both stages gather one query row per pair from the Infinity Cache at ~6 TB/s, which is the
+    // bound (profiles/r03_prefilter_attribution.md).  Kept because it pays once the survivor share drops
+    // (descriptors with outlier coordinates widen the int8 bound, not the fp16 one).
+    if (!(from_i8 && idx->i8_screen && n_c > 0)) return launch_rescore_dense(r, sj, si, (long long)n_c, idx->stream);
+    ScreenArgs sa;
+    sa.Qh = ws.qh.as<_Float16>();
+    sa.qn = ws.qn.as<float>();
+    sa.Rh = idx->refh.as<_Float16>();
+    sa.rn = idx->refn.as<float>();
+    sa.dpadh = idx->dpadh;
+    sa.frag = idx->frag ? 1 : 0;
+    sa.c1 = fb.c1; sa.c2 = fb.c2; sa.c3 = fb.c3;
+    sa.radius = &ctl->radius;
+    sa.row_thr = b.row_thr;
+    sa.sj = sj;
+    sa.si = si;
+    sa.n = (long long)n_c;
+    sa.out_j = sj == cs[0] ? cs[1] : cs[0];
+    sa.out_i = si == cs[2] ? cs[3] : cs[2];
+    sa.n_out = csn + 1;
+    sa.n_cand_total = &ctl->n_cand_total;
+    sa.overflow = &ctl->overflow;
+    VSC_TRY(launch_f16_screen(sa, idx->stream));
+    VSC_TRY(launch_rescore_dense(r, sa.out_j, sa.out_i, (long long)n_c, idx->stream, sa.n_out));
+    if (idx->debug_screen) {
+        unsigned long long n_s = 0;
+        VSC_HIP(hipMemcpyAsync(&n_s, sa.n_out, sizeof(n_s), hipMemcpyDeviceToHost, idx->stream));
+        VSC_HIP(hipStreamSynchronize(idx->stream));
+        fprintf(stderr, "[vscmi] fp16 screen: %llu of %llu int8 candidates left (rows %d)\n", n_s, n_c, b.nq);
+    }
+    return VSC_OK;
+}
 
 // fp16 pre-filter + exact re-scoring of query rows [i0, i1): appends to hit buffer A every (row, ref, score)
 // with score > *radius -- or, when `row_thr` (one threshold per query row, padded like the fp16 query
@@ -48,268 +310,21 @@ int enqueue_f16(vsc_index* idx, const float* qpacked, int64_t i0, int64_t i1, in
         set_error("enqueue_f16: reference range [%lld, %lld) does not start on a 64-row tile", (long long)nr_begin, (long long)nr_end);
         return VSC_ERR_INVALID;
     }
-    const int64_t nrefs = nr_end - nr_begin;  // rows the kernels see
-    SelectCtl* ctl = idx->ws.ctl.as<SelectCtl>();
-    const int nqb = (int)(i1 - i0);
-    {
-        // 1. fp16 pre-filter: candidates = pairs whose fp16 score + error bound exceeds the threshold
-        const double D = (double)idx->dpadh;
-        // |fp16 score - exact score| <= c1 |q||r| + c2 (|q| + |r|) + c3   (|x| = L2 norm):
-        //   rounding to fp16: |x - h(x)| <= 2^-11 |x| + 2^-25 per element (normal / subnormal range)
-        //     => sum |q r - h(q) h(r)| <= (2^-10 + 2^-22) |q||r| + 2^-25 * 1.001 * sqrt(D) (|q|+|r|) + D 2^-50
-        //   accumulation: the exact fp32 fma chain (D roundings) and the MFMA's fp32 accumulation
-        //     (D/16 instructions of 16 products + addend) each stay within 2^-23 |q||r| per operation
-        const float c1 = (float)(ldexp(1.0, -10) + ldexp(1.0, -22) + (2.0 * D + D / 16.0 + 16.0) * ldexp(1.0, -23));
-        const float c2 = (float)(ldexp(1.0, -25) * 1.001 * sqrt(D));
-        const float c3 = (float)(D * ldexp(1.0, -50));
-        int grid = 0;
-        CandList cl;
-        const int32_t* cand_perm = nullptr;  // set when the candidate list holds positions of a permuted int8 launch
-        hipEvent_t stop;
-        int pcls = 1;
-        if (use_i8 && idx->i8_mode) {
-            // int8 panel kernel (sim_i8p.hip): this launch's rows are quantised first, one scale per 128-row panel
-            SimI8PArgs f;
-            sim_f16p_plan(nqb, nrefs, &f.npanel, &f.nsteps, &f.slice, &grid);
-            {
-                // work order: slice-major items.  r03 (32x32x32 kernel): items of 16 col-steps (4 MiB of the int8 image at
-                // 512-d: what an XCD's L2 holds) +3 % on the bench over panel-major (2431 -> 2507-2515 TOP/s).  r04
-                // (16x16x64 kernel, configs[3]): 8 / 16 / 32 / 64 col-steps 2456 / 2390 / 2363 / 2368 ms per query set
-                // -- the faster K loop makes the hand-over (panel load + two barriers) the larger share: 32.
-                // VSC_I8P_ORDER=0: panel-major with stealing as in sim_f16p
-                const int slice_env = idx->i8p_slice;
-                f.order = idx->i8p_order;
-                if (f.order == 1) f.slice = std::max(1, std::min(f.nsteps, slice_env > 0 ? slice_env : 32));
-                else if (slice_env > 0) f.slice = std::max(1, std::min(f.nsteps, slice_env));
-            }
-            // work items of two panels (wave tiles of 256 rows x 32 columns: half the reference bytes per MFMA) where the
-            // launch is large enough; the quantised image then holds an even number of panels.  VSC_I8P_PAIR=0: off
-            f.pair = idx->i8p_pair && sim_i8p_pairs(idx->dpad8, f.npanel, f.nsteps, f.slice, idx->i8p_pair == 2) ? 1 : 0;
-            const int npanel_q = f.pair ? (f.npanel + 1) & ~1 : f.npanel;
-            VSC_TRY(idx->ws.slices.reserve(((size_t)f.npanel + 1) * sizeof(int)));
-            VSC_TRY(idx->ws.q8.reserve((size_t)npanel_q * F16P_PANEL_ROWS * idx->dpad8));
-            VSC_TRY(idx->ws.pstat.reserve((size_t)npanel_q * sizeof(float4)));
-            hipEvent_t prep_stop;
-            VSC_TRY(prof_begin(idx, &prep_stop, 6));
-            const int32_t* perm = nullptr;
-            float* rt_pos = nullptr;
-            const float* thr_src = row_thr ? row_thr + i0 : nullptr;
-            if (idx->i8_ex.n > 0 || idx->i8_mu_on) {
-                // coordinates the images leave out (all references agree on them) act through the rows' thresholds:
-                // t_row - sum_c q_c v_c, with t_row the row's k-NN threshold or the search radius; a centred reference
-                // image (quant_i8.hip) adds the rows' x . mu the same way
-                VSC_TRY(idx->ws.rt8b.reserve((size_t)nqb * sizeof(float)));
-                const float *cen = nullptr, *cmag = nullptr;
-                if (idx->i8_mu_on) {
-                    VSC_TRY(idx->ws.rt8d.reserve((size_t)2 * nqb * sizeof(float)));
-                    VSC_TRY(launch_row_center(qpacked + i0 * idx->dpad, idx->dpad, nqb, idx->i8_mu.as<float>(),
-                                              idx->ws.rt8d.as<float>(), idx->ws.rt8d.as<float>() + nqb, idx->stream));
-                    cen = idx->ws.rt8d.as<float>();
-                    cmag = cen + nqb;
-                }
-                VSC_TRY(launch_row_bias_thresholds(qpacked + i0 * idx->dpad, idx->dpad, nqb, thr_src, &ctl->radius,
-                                                   idx->i8_ex, cen, cmag, idx->ws.rt8b.as<float>(), idx->stream));
-                thr_src = idx->ws.rt8b.as<float>();
-            }
-            // VSC_I8_SORT=0: rows in their own order (A/B; the kernel then gates blocks of unrelated thresholds)
-            const bool sort_rows = idx->i8_sort_rows;
-            if (thr_src && !sort_rows) {
-                VSC_TRY(idx->ws.rt8.reserve((size_t)npanel_q * F16P_PANEL_ROWS * sizeof(float)));
-                rt_pos = idx->ws.rt8.as<float>();
-            } else if (thr_src) {
-                // thresholds that differ from row to row: the launch sees its rows sorted by threshold (the kernel
-                // gates a tile by its panel's smallest threshold and a 16-row block by the block's)
-                VSC_TRY(idx->ws.rt8.reserve((size_t)npanel_q * F16P_PANEL_ROWS * sizeof(float)));
-                rt_pos = idx->ws.rt8.as<float>();
-                if (idx->i8_group_shift > 0 && !row_thr && nqb >= (4 << idx->i8_group_shift)) {
-                    // ... and, inside groups of 512 positions of that order, by the rows' largest element (sortpairs.hip).
-                    // Only for the radius search over excluded coordinates (thresholds = radius - the rows' bias: a
-                    // narrow spread): configs[3] 1162 -> 1086 M candidates, exact stage 367 -> 341 ms (groups of 256 /
-                    // 512 / 1024 / 2048 / 4096: 1110 / 1086 / 1090 / 1125 / 1205 M).  The k-NN's thresholds -- each
-                    // row's best score so far -- spread far more: there the same grouping cost 2 % (892 -> 907 ms).
-                    VSC_TRY(idx->ws.rt8c.reserve((size_t)nqb * sizeof(float)));
-                    VSC_TRY(launch_row_absmax(qpacked + i0 * idx->dpad, idx->dpad, nqb, idx->i8_ex, idx->ws.rt8c.as<float>(),
-                                              idx->stream));
-                    VSC_TRY(sort_rows_by_threshold_then_scale(thr_src, idx->ws.rt8c.as<float>(), nqb, idx->i8_group_shift,
-                                                              idx->ws.w0, idx->ws.w1, idx->ws.w2, idx->ws.w3, idx->ws.tmp,
-                                                              &perm, idx->stream));
-                } else
-                VSC_TRY(sort_rows_by_threshold(thr_src, nqb, idx->ws.w0, idx->ws.w1, idx->ws.w2, idx->ws.w3, idx->ws.tmp,
-                                               &perm, idx->stream));
-            }
-            else if (sort_rows && nqb >= 2 * F16P_PANEL_ROWS) {
-                // one threshold for all rows (the search radius): sort by the rows' largest element instead, so that
-                // a panel's shared scale is close to what each of its rows would have chosen (VSC_I8_SORT=0: off)
-                VSC_TRY(idx->ws.rt8b.reserve((size_t)nqb * sizeof(float)));
-                VSC_TRY(launch_row_absmax(qpacked + i0 * idx->dpad, idx->dpad, nqb, idx->i8_ex, idx->ws.rt8b.as<float>(),
-                                          idx->stream));
-                VSC_TRY(sort_rows_by_threshold(idx->ws.rt8b.as<float>(), nqb, idx->ws.w0, idx->ws.w1, idx->ws.w2, idx->ws.w3,
-                                               idx->ws.tmp, &perm, idx->stream));
-            }
-            VSC_TRY(launch_quant_query_panels(qpacked + i0 * idx->dpad, idx->dpad, nqb, npanel_q, idx->ws.q8.p, idx->dpad8,
-                                              idx->ws.pstat.as<float4>(), perm, thr_src, rt_pos, idx->i8_ex, idx->stream));
-            f.Q = idx->ws.q8.p;
-            f.pstat = idx->ws.pstat.as<float4>();
-            f.Rf = static_cast<const char*>(idx->ref8.p) + nr_begin * idx->dpad8;  // (whole 64-row tiles: dpad8 x 64 B each)
-            f.rmeta = idx->ref8m.as<float4>() + nr_begin;
-            f.dpad8 = idx->dpad8;
-            f.nq = nqb;
-            f.i0 = (int)i0;
-            f.nr = (int)nrefs;
-            f.next_slice = idx->ws.slices.as<int>();
-            // the exact fp32 chain is within dpad 2^-24 |q||r| (1 + tiny) of the real inner product
-            f.c_acc = (float)(((double)idx->dpad + 2.0) * ldexp(1.0, -23));
-            f.radius = &ctl->radius;
-            f.row_thr = rt_pos;
-            cand_perm = perm;
-            VSC_TRY(cand_list_setup(idx, ccap, grid, f, cl));
-            VSC_TRY(prof_end(idx, prep_stop, 0.0, 6));
-            VSC_TRY(prof_begin(idx, &stop, 5));  // (the kernel alone: what the roofline figure is about)
-            VSC_TRY(launch_sim_i8p(f, grid, idx->stream));
-            pcls = 5;
-        } else if (idx->frag) {
-            // panel-stationary kernel (sim_f16p.hip): LDS-resident query panels x the fragment-major reference image
-            SimF16PArgs f;
-            sim_f16p_plan(nqb, nrefs, &f.npanel, &f.nsteps, &f.slice, &grid);
-            VSC_TRY(idx->ws.slices.reserve((size_t)f.npanel * sizeof(int)));
-            f.Q = idx->ws.qh.as<_Float16>() + i0 * idx->dpadh;
-            f.Rf = static_cast<const char*>(idx->refh.p) + nr_begin * idx->dpadh * 2;
-            f.qn = idx->ws.qn.as<float>() + i0;
-            f.rn = idx->refn.as<float>() + nr_begin;
-            f.dpadh = idx->dpadh;
-            f.nq = nqb;
-            f.i0 = (int)i0;
-            f.nr = (int)nrefs;
-            f.next_slice = idx->ws.slices.as<int>();
-            f.c1 = c1; f.c2 = c2; f.c3 = c3;
-            f.radius = &ctl->radius;
-            f.row_thr = row_thr ? row_thr + i0 : nullptr;
-            VSC_TRY(cand_list_setup(idx, ccap, grid, f, cl));
-            VSC_TRY(prof_begin(idx, &stop, 1));
-            VSC_TRY(launch_sim_f16p(f, grid, idx->stream));
-        } else {
-            // dims > 512: 256x256 LDS-ring kernel (sim_f16.hip) on the natural image
-            SimF16Args f;
-            f.Q = idx->ws.qh.as<_Float16>() + i0 * idx->dpadh;
-            f.R = idx->refh.as<_Float16>() + nr_begin * idx->dpadh;
-            f.qn = idx->ws.qn.as<float>() + i0;
-            f.rn = idx->refn.as<float>() + nr_begin;
-            f.dpadh = idx->dpadh;
-            f.nq = nqb;
-            f.i0 = (int)i0;
-            f.nr = (int)nrefs;
-            f.tq = (nqb + 255) / 256;
-            f.tr = (int)((nrefs + 255) / 256);
-            f.c1 = c1; f.c2 = c2; f.c3 = c3;
-            f.radius = &ctl->radius;
-            f.row_thr = row_thr ? row_thr + i0 : nullptr;
-            grid = sim_f16_grid(f.tq, f.tr);
-            VSC_TRY(cand_list_setup(idx, ccap, grid, f, cl));
-            VSC_TRY(prof_begin(idx, &stop, 1));
-            VSC_TRY(launch_sim_f16(f, idx->stream));
-        }
-        VSC_TRY(prof_end(idx, stop, 2.0 * (double)nqb * (double)nrefs * (double)idx->dim, pcls));
-        // 2. exact scores of the candidates; those above the radius join the kept hits
-        RescoreArgs r;
-        r.Q = qpacked;
-        r.R = idx->ref.as<float>();
-        r.dpad = idx->dpad;
-        r.cand_i = idx->ws.ci.as<int32_t>();
-        r.cand_j = idx->ws.cj.as<int32_t>();
-        r.n_seg = cl.grid * 8;
-        r.seg_cap = cl.seg_cap;
-        r.seg_count = idx->ws.segcnt.as<int>();
-        r.tail_base = cl.tail_base;
-        r.tail_cap = cl.tail_cap;
-        r.tail_count = &ctl->n_tail;
-        r.tail_shift = cl.tail_shift;
-        r.tail_fill = idx->ws.tailfill.as<int>();
-        r.perm = cand_perm;
-        r.perm_i0 = (int)i0;
-        r.n_cand_total = &ctl->n_cand_total;
-        r.radius = &ctl->radius;
-        r.out_i = idx->ws.hA[0].as<int32_t>();
-        r.out_j = idx->ws.hA[1].as<int32_t>();
-        r.out_s = idx->ws.hA[2].as<float>();
-        r.counter = &ctl->n;
-        r.cap = cap;
-        r.overflow = &ctl->overflow;
-        r.row_thr = row_thr;
-        r.j0 = (int)nr_begin;
-        if (sq16(idx)) {  // the reference rows come from the fp16 store (sim_f16.hip: rescore_list<SRC>)
-            r.R = nullptr;
-            r.Rh = idx->refh.as<_Float16>();
-            r.dpadh = idx->dpadh;
-            r.rsrc = idx->frag ? 2 : 1;
-        }
-        VSC_TRY(prof_begin(idx, &stop, 2));
-        // The candidates are compacted out of the waves' segments, sorted by reference row and re-scored as one dense
-        // list (sim_f16.hip, "candidates ordered by reference row"): 74 -> 54 ms per bench step, k-NN k = 20 140 ->
-        // 100 ms.  It needs the candidate count on the host (buffer sizes, grid of the sort): one stream sync per
-        // launch, ~20 us against launches of 3-30 ms.  VSC_RESCORE_SORT=0: the segments as they are.
-        const bool by_ref = idx->rescore_by_ref;
-        if (by_ref) {
-            // count first (one tiny kernel + the stream sync the sort needs anyway), then size the four dense lists of
-            // the sort from what the launch really left behind -- not from the list's capacity (96 bytes
-            // per unit of capacity, 26 GB for a default range search whose launches hold a few percent of that)
-            VSC_TRY(idx->ws.csn.reserve(3 * sizeof(unsigned long long)));
-            const int n_chunks_max = (int)std::min<long long>((cl.tail_cap >> cl.tail_shift) + 1, 1 << 20);
-            VSC_TRY(launch_cand_count(r, n_chunks_max, idx->ws.csn.as<unsigned long long>() + 2, idx->stream));
-            unsigned long long n_c = 0;
-            VSC_HIP(hipMemcpyAsync(&n_c, idx->ws.csn.as<unsigned long long>() + 2, sizeof(n_c), hipMemcpyDeviceToHost, idx->stream));
-            VSC_HIP(hipStreamSynchronize(idx->stream));
-            // (grown in steps of a quarter so that launches of slowly varying size do not reallocate every time)
-            const size_t cap_e = (size_t)(n_c + n_c / 4 + 4096);
-            for (auto& b : idx->ws.cs)
-                if (b.bytes < (size_t)(n_c + 1) * sizeof(uint32_t)) VSC_TRY(b.reserve(cap_e * sizeof(uint32_t)));
-            VSC_TRY(launch_cand_compact(r, n_chunks_max, idx->ws.cs[0].as<uint32_t>(), idx->ws.cs[2].as<uint32_t>(),
-                                        idx->ws.csn.as<unsigned long long>(), idx->stream));
-            const uint32_t *sj = nullptr, *si = nullptr;
-            VSC_TRY(sort_candidates_by_ref(idx->ws.cs[0].as<uint32_t>(), idx->ws.cs[1].as<uint32_t>(), idx->ws.cs[2].as<uint32_t>(),
-                                           idx->ws.cs[3].as<uint32_t>(), (int64_t)n_c, nr_end, idx->ws.cstmp, &sj, &si, idx->stream));
-            // VSC_I8_SCREEN=1: int8 launches pass an fp16 screen first (sim_f16.hip: f16_screen_kernel).  Measured
-            // neutral and therefore OFF by default: 29 % of the int8 candidates survive it (bench, 128 M -> 37 M per
-            // step), the screen moves half the bytes per pair (23.8 ms) and the exact stage then costs 35.6 instead of
-            // 59.8 ms -- both stages gather one query row per pair from the Infinity Cache at ~6 TB/s, which is the
-            // bound (profiles/r03_prefilter_attribution.md).  Kept because it pays once the survivor share drops
-            // (descriptors with outlier coordinates widen the int8 bound, not the fp16 one).
-            const bool screen = idx->i8_screen;
-            if (pcls == 5 && screen && n_c > 0) {
-                ScreenArgs sa;
-                sa.Qh = idx->ws.qh.as<_Float16>();
-                sa.qn = idx->ws.qn.as<float>();
-                sa.Rh = idx->refh.as<_Float16>();
-                sa.rn = idx->refn.as<float>();
-                sa.dpadh = idx->dpadh;
-                sa.frag = idx->frag ? 1 : 0;
-                sa.c1 = c1; sa.c2 = c2; sa.c3 = c3;
-                sa.radius = &ctl->radius;
-                sa.row_thr = row_thr;
-                sa.sj = sj;
-                sa.si = si;
-                sa.n = (long long)n_c;
-                sa.out_j = sj == idx->ws.cs[0].as<uint32_t>() ? idx->ws.cs[1].as<uint32_t>() : idx->ws.cs[0].as<uint32_t>();
-                sa.out_i = si == idx->ws.cs[2].as<uint32_t>() ? idx->ws.cs[3].as<uint32_t>() : idx->ws.cs[2].as<uint32_t>();
-                sa.n_out = idx->ws.csn.as<unsigned long long>() + 1;
-                sa.n_cand_total = &ctl->n_cand_total;
-                sa.overflow = &ctl->overflow;
-                VSC_TRY(launch_f16_screen(sa, idx->stream));
-                VSC_TRY(launch_rescore_dense(r, sa.out_j, sa.out_i, (long long)n_c, idx->stream, sa.n_out));
-                if (idx->debug_screen) {
-                    unsigned long long n_s = 0;
-                    VSC_HIP(hipMemcpyAsync(&n_s, sa.n_out, sizeof(n_s), hipMemcpyDeviceToHost, idx->stream));
-                    VSC_HIP(hipStreamSynchronize(idx->stream));
-                    fprintf(stderr, "[vscmi] fp16 screen: %llu of %llu int8 candidates left (rows %d)\n", n_s, n_c, nqb);
-                }
-            } else {
-                VSC_TRY(launch_rescore_dense(r, sj, si, (long long)n_c, idx->stream));
-            }
-        } else {
-            VSC_TRY(launch_rescore(r, idx->stream));
-        }
-        VSC_TRY(prof_end(idx, stop, 0.0, 2));
-    }
-    return VSC_OK;
+    const F16Batch b{qpacked, i0, (int)(i1 - i0), row_thr, nr_begin, nr_end};
+    const F16Bound fb = f16_bound(idx->dpadh);
+    // 1. pre-filter: candidates = pairs whose low-precision score + error bound reaches the threshold
+    const bool i8 = use_i8 && idx->i8_mode;
+    CandList cl;
+    const int32_t* perm = nullptr;
+    hipEvent_t stop;
+    if (i8) VSC_TRY(prefilter_i8(idx, b, ccap, cl, &perm, &stop));
+    else if (idx->frag) VSC_TRY(prefilter_f16_panel(idx, b, ccap, fb, cl, &stop));
+    else VSC_TRY(prefilter_f16_ring(idx, b, ccap, fb, cl, &stop));
+    VSC_TRY(prof_end(idx, stop, 2.0 * (double)b.nq * (double)b.nrefs() * (double)idx->dim, i8 ? 5 : 1));
+    // 2. exact scores of the candidates; those above the radius join the kept hits
+    VSC_TRY(prof_begin(idx, &stop, 2));
+    VSC_TRY(exact_stage(idx, b, cap, cl, perm, fb, i8));
+    return prof_end(idx, stop, 0.0, 2);
 }
 
 // Append every (row, ref) of query rows [i0, i1) with score > *radius (score space: IP as is, L2
@@ -318,49 +333,41 @@ static int enqueue_batch(vsc_index* idx, const float* qpacked, int64_t i0, int64
                          bool use_f16 = false, bool use_i8 = false) {
     SelectCtl* ctl = idx->ws.ctl.as<SelectCtl>();
     const int nqb = (int)(i1 - i0);
+    const HitView kept = idx->ws.hits_a();
     if (use_f16) return enqueue_f16(idx, qpacked, i0, i1, cap, nullptr, -1, -1, use_i8);
     if (idx->metric == VSC_METRIC_INNER_PRODUCT) {
         SimThreshArgs a;
         a.Q = qpacked + i0 * idx->dpad;
-        a.R = idx->ref.as<float>();
         a.dpad = idx->dpad;
         a.nq = nqb;
         a.i0 = (int)i0;
-        a.nr = (int)idx->ntotal;
         a.tq = (nqb + 127) / 128;
-        a.tr = (int)((idx->ntotal + 127) / 128);
         a.radius = &ctl->radius;
-        a.out_i = idx->ws.hA[0].as<int32_t>();
-        a.out_j = idx->ws.hA[1].as<int32_t>();
-        a.out_s = idx->ws.hA[2].as<float>();
+        a.out_i = kept.i;
+        a.out_j = kept.j;
+        a.out_s = kept.s;
         a.counter = &ctl->n;
         a.cap = cap;
         a.overflow = &ctl->overflow;
-        hipEvent_t stop;
-        if (sq16(idx)) {
-            // the kernel streams whole packed rows: bounded ranges of the store are decoded for it, one after the other;
-            // the hits a range appends carry refs relative to it and get the range's offset afterwards
-            VSC_TRY(idx->ws.flag.reserve(16));
-            unsigned long long* mark = idx->ws.flag.as<unsigned long long>() + 1;
-            for (int64_t j0 = 0; j0 < idx->ntotal; j0 += DEC_CHUNK_ROWS) {
-                const int64_t rows = std::min(DEC_CHUNK_ROWS, idx->ntotal - j0);
-                float* dec = nullptr;
-                VSC_TRY(decode_range(idx, j0, rows, &dec));
-                a.R = dec;
-                a.nr = (int)rows;
-                a.tr = (int)((rows + 127) / 128);
-                if (j0 > 0) VSC_TRY(launch_hits_mark(&ctl->n, mark, idx->stream));
-                VSC_TRY(prof_begin(idx, &stop));
-                VSC_TRY(launch_sim_thresh(a, idx->stream));
-                VSC_TRY(prof_end(idx, stop, 2.0 * (double)nqb * (double)rows * (double)idx->dim));
-                if (j0 > 0) VSC_TRY(launch_hits_add_offset(a.out_j, mark, &ctl->n, cap, (int)j0, idx->stream));
+        // the kernel streams whole packed rows, one range of them after the other; the hits a range after the first
+        // appends carry refs relative to it and get the range's offset afterwards
+        return for_ref_ranges(idx, 0, idx->ntotal, [&](const float* rows, int64_t j0, int64_t n) -> int {
+            unsigned long long* mark = nullptr;
+            if (j0 > 0) {
+                VSC_TRY(idx->ws.flag.reserve(16));
+                mark = idx->ws.flag.as<unsigned long long>() + 1;
+                VSC_TRY(launch_hits_mark(&ctl->n, mark, idx->stream));
             }
+            a.R = rows;
+            a.nr = (int)n;
+            a.tr = (int)((n + 127) / 128);
+            hipEvent_t stop;
+            VSC_TRY(prof_begin(idx, &stop));
+            VSC_TRY(launch_sim_thresh(a, idx->stream));
+            VSC_TRY(prof_end(idx, stop, 2.0 * (double)nqb * (double)n * (double)idx->dim));
+            if (j0 > 0) VSC_TRY(launch_hits_add_offset(a.out_j, mark, &ctl->n, cap, (int)j0, idx->stream));
             return VSC_OK;
-        }
-        VSC_TRY(prof_begin(idx, &stop));
-        VSC_TRY(launch_sim_thresh(a, idx->stream));
-        VSC_TRY(prof_end(idx, stop, 2.0 * (double)nqb * (double)idx->ntotal * (double)idx->dim));
-        return VSC_OK;
+        });
     }
     // generic metric: explicit score matrix in row chunks
     const int64_t nr = idx->ntotal;
@@ -372,8 +379,7 @@ static int enqueue_batch(vsc_index* idx, const float* qpacked, int64_t i0, int64
                        idx->metric, idx->ws.mat.as<float>()};
         if (sq16(idx)) VSC_TRY(launch_score_matrix_h16(m, idx->refh.as<_Float16>(), idx->dpadh, idx->frag, idx->stream));
         else VSC_TRY(launch_score_matrix(m, idx->stream));
-        MatThreshArgs t{idx->ws.mat.as<float>(), rows, (int)nr, (int)r0, &ctl->radius,
-                        idx->ws.hA[0].as<int32_t>(), idx->ws.hA[1].as<int32_t>(), idx->ws.hA[2].as<float>(),
+        MatThreshArgs t{idx->ws.mat.as<float>(), rows, (int)nr, (int)r0, &ctl->radius, kept.i, kept.j, kept.s,
                         &ctl->n, cap, &ctl->overflow};
         VSC_TRY(launch_matrix_thresh(t, idx->stream));
     }
@@ -445,10 +451,7 @@ static int global_topk_impl(vsc_index_t* idx, const float* q, int64_t nq, int q_
             if (i1 < nq) {
                 hipEvent_t stop;
                 VSC_TRY(prof_begin(idx, &stop, 3));
-                VSC_TRY(enqueue_rethreshold(ctl, idx->ws.hA[0].as<int32_t>(), idx->ws.hA[1].as<int32_t>(),
-                                            idx->ws.hA[2].as<float>(), idx->ws.hB[0].as<int32_t>(),
-                                            idx->ws.hB[1].as<int32_t>(), idx->ws.hB[2].as<float>(),
-                                            (unsigned long long)K, idx->stream));
+                VSC_TRY(enqueue_rethreshold(ctl, idx->ws.hits_a(), idx->ws.hits_b(), (unsigned long long)K, idx->stream));
                 VSC_TRY(prof_end(idx, stop, 0.0, 3));
             }
             if (!seeded && bs < 20000) bs *= 2;
@@ -459,10 +462,7 @@ static int global_topk_impl(vsc_index_t* idx, const float* q, int64_t nq, int q_
         if (!h.overflow && h.n > 2ull * (unsigned long long)K) {
             hipEvent_t stop;
             VSC_TRY(prof_begin(idx, &stop, 3));
-            VSC_TRY(enqueue_rethreshold(ctl, idx->ws.hA[0].as<int32_t>(), idx->ws.hA[1].as<int32_t>(),
-                                        idx->ws.hA[2].as<float>(), idx->ws.hB[0].as<int32_t>(),
-                                        idx->ws.hB[1].as<int32_t>(), idx->ws.hB[2].as<float>(),
-                                        (unsigned long long)K, idx->stream));
+            VSC_TRY(enqueue_rethreshold(ctl, idx->ws.hits_a(), idx->ws.hits_b(), (unsigned long long)K, idx->stream));
             VSC_TRY(prof_end(idx, stop, 0.0, 3));
             VSC_HIP(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, idx->stream));
             VSC_HIP(hipStreamSynchronize(idx->stream));
@@ -498,39 +498,32 @@ static int global_topk_impl(vsc_index_t* idx, const float* q, int64_t nq, int q_
         set_error("global_topk: output capacity %lld < %lld", (long long)cap_out, (long long)m);
         return VSC_ERR_CAPACITY;
     }
-    int32_t *di = out_i, *dj = out_j;
-    float* ds = out_s;
+    HitView d{out_i, out_j, out_s};
     if (out_mem == VSC_MEM_HOST) {
-        VSC_TRY(idx->ws.out[0].reserve((size_t)std::max<int64_t>(m, 1) * 4));
-        VSC_TRY(idx->ws.out[1].reserve((size_t)std::max<int64_t>(m, 1) * 4));
-        VSC_TRY(idx->ws.out[2].reserve((size_t)std::max<int64_t>(m, 1) * 4));
-        di = idx->ws.out[0].as<int32_t>();
-        dj = idx->ws.out[1].as<int32_t>();
-        ds = idx->ws.out[2].as<float>();
+        for (int c = 0; c < 3; ++c) VSC_TRY(idx->ws.out[c].reserve((size_t)std::max<int64_t>(m, 1) * 4));
+        d = idx->ws.hits_out();
     }
     int64_t mm = 0;
     hipEvent_t sort_stop;
     VSC_TRY(prof_begin(idx, &sort_stop, 4));
     if (idx->sort_hits || !ip) {
-        VSC_TRY(sort_hits_topk(idx->ws.hA[0].as<int32_t>(), idx->ws.hA[1].as<int32_t>(), idx->ws.hA[2].as<float>(),
-                               n, K, nq, idx->ntotal, idx->ws.w0, idx->ws.w1, idx->ws.w2, idx->ws.w3, idx->ws.tmp, di, dj, ds,
-                               ip ? 0 : 1, &mm, idx->stream));
+        VSC_TRY(sort_hits_topk(idx->ws.hits_a(), n, K, nq, idx->ntotal, idx->ws.sort, d, ip ? 0 : 1, &mm, idx->stream));
     } else {
         // option "sort_hits" = 0 (the column-sharded schedule, vsc2022_amd/dist.py: a batch's hits only join a list that
         // is counted, filtered and sorted ONCE at the end; inner product only): the kept hits as they lie; a
         // list of K entries may be a truncated one (n > K) -- the caller then asks again with a larger budget
         mm = m;
         if (mm > 0) {
-            VSC_HIP(hipMemcpyAsync(di, idx->ws.hA[0].p, (size_t)mm * 4, hipMemcpyDeviceToDevice, idx->stream));
-            VSC_HIP(hipMemcpyAsync(dj, idx->ws.hA[1].p, (size_t)mm * 4, hipMemcpyDeviceToDevice, idx->stream));
-            VSC_HIP(hipMemcpyAsync(ds, idx->ws.hA[2].p, (size_t)mm * 4, hipMemcpyDeviceToDevice, idx->stream));
+            VSC_HIP(hipMemcpyAsync(d.i, idx->ws.hA[0].p, (size_t)mm * 4, hipMemcpyDeviceToDevice, idx->stream));
+            VSC_HIP(hipMemcpyAsync(d.j, idx->ws.hA[1].p, (size_t)mm * 4, hipMemcpyDeviceToDevice, idx->stream));
+            VSC_HIP(hipMemcpyAsync(d.s, idx->ws.hA[2].p, (size_t)mm * 4, hipMemcpyDeviceToDevice, idx->stream));
         }
     }
     VSC_TRY(prof_end(idx, sort_stop, 12.0 * (double)n, 4));  // (row, ref, score) of every kept hit in
     if (out_mem == VSC_MEM_HOST && mm > 0) {
-        VSC_HIP(hipMemcpyAsync(out_i, di, (size_t)mm * 4, hipMemcpyDeviceToHost, idx->stream));
-        VSC_HIP(hipMemcpyAsync(out_j, dj, (size_t)mm * 4, hipMemcpyDeviceToHost, idx->stream));
-        VSC_HIP(hipMemcpyAsync(out_s, ds, (size_t)mm * 4, hipMemcpyDeviceToHost, idx->stream));
+        VSC_HIP(hipMemcpyAsync(out_i, d.i, (size_t)mm * 4, hipMemcpyDeviceToHost, idx->stream));
+        VSC_HIP(hipMemcpyAsync(out_j, d.j, (size_t)mm * 4, hipMemcpyDeviceToHost, idx->stream));
+        VSC_HIP(hipMemcpyAsync(out_s, d.s, (size_t)mm * 4, hipMemcpyDeviceToHost, idx->stream));
     }
     VSC_HIP(hipStreamSynchronize(idx->stream));
     VSC_TRY(prof_collect(idx));
@@ -693,7 +686,7 @@ int vsc_index_candidates(vsc_index_t* idx, const float* q, int64_t nq, int q_mem
     VSC_TRY(ws.out[3].reserve((size_t)n * 8));
     int64_t np = 0;
     VSC_TRY(pair_max_device(idx->cand[0].as<int32_t>(), idx->cand[1].as<int32_t>(), idx->cand[2].as<float>(), n,
-                            ws.maps0.as<int32_t>(), ws.maps1.as<int32_t>(), nq, idx->ntotal, ws.w0, ws.w1, ws.w2, ws.w3, ws.tmp,
+                            ws.maps0.as<int32_t>(), ws.maps1.as<int32_t>(), nq, idx->ntotal, ws.sort,
                             ws.cnt, ws.out[0].as<int32_t>(), ws.out[1].as<int32_t>(), ws.out[2].as<float>(),
                             ws.out[3].as<int64_t>(), n, &np, idx->stream));
     *n_pairs = np;
@@ -746,9 +739,7 @@ int vsc_index_range_search(vsc_index_t* idx, const float* q, int64_t nq, int q_m
     *n_out = n;
     if (n == 0) return VSC_OK;
     // rows ascending, refs ascending (reuse B as the sorted target)
-    VSC_TRY(sort_hits_rowcol(idx->ws.hA[0].as<int32_t>(), idx->ws.hA[1].as<int32_t>(), idx->ws.hA[2].as<float>(), n,
-                             idx->ws.w0, idx->ws.w1, idx->ws.w2, idx->ws.w3, idx->ws.tmp, idx->ws.hB[0].as<int32_t>(),
-                             idx->ws.hB[1].as<int32_t>(), idx->ws.hB[2].as<float>(), ip ? 0 : 1, idx->stream));
+    VSC_TRY(sort_hits_rowcol(idx->ws.hits_a(), n, idx->ws.sort, idx->ws.hits_b(), ip ? 0 : 1, idx->stream));
     std::vector<int32_t> hi((size_t)n);
     VSC_HIP(hipMemcpyAsync(hi.data(), idx->ws.hB[0].p, (size_t)n * 4, hipMemcpyDeviceToHost, idx->stream));
     VSC_HIP(hipStreamSynchronize(idx->stream));

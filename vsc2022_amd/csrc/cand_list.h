@@ -9,6 +9,20 @@
 
 namespace vscmi {
 
+// The whole list of one pre-filter launch, as the host plans it (api_search.hip: cand_list_plan) and as the pre-filter
+// kernels and the exact stage read it: SimF16Args, SimF16PArgs, SimI8PArgs and RescoreArgs each hold one.  One type
+// for the writers and the readers: the pointers are not const, though the exact stage only reads the entries and
+// fill levels (it resets tail_count).
+struct CandList {
+    int32_t* i; int32_t* j;          // the two entry arrays: (row, ref) of a candidate
+    // one private segment of seg_cap entries per wave of the launch (8 per workgroup), seg_count[w] = its fill level
+    int n_seg; int seg_cap; int* seg_count;
+    // the shared tail behind the segments, for waves whose segment is full: entries [tail_base, tail_base + tail_cap),
+    // handed out in chunks of 1 << tail_shift entries, each with a fill level; tail_count = entries handed out
+    int64_t tail_base; long long tail_cap; int tail_shift; int* tail_fill; unsigned long long* tail_count;
+    int* overflow;                   // bit 1: the tail is exhausted (bit 0 belongs to the kept-hit list)
+};
+
 // The wave's tail state lives in LDS, not in registers: it is touched only on the rare "segment full" path, and the
 // pre-filter kernels have no register to spare.  The code below is inlined 128 times into fully unrolled loops over
 // the accumulator registers: it must stay loop-free -- with a loop inside, the compiler stopped unrolling the outer
@@ -28,29 +42,27 @@ __device__ __forceinline__ void tail_init(TailExt* e, int ln) {
 // Room for `total` (<= 64) more candidates of this wave behind its full segment: true and `pos` = first entry, or
 // false (tail exhausted: bit 1 of *overflow is set -- bit 0 belongs to the kept-hit list -- and the host reruns the
 // search on the fp16 kernel or with larger buffers).  Wave-uniform arguments; ln = lane;
-// `e` = the wave's slot in LDS (one wave reads and writes it, in program order); chunk = 1 << chunk_shift.
-__device__ __forceinline__ bool tail_take(unsigned long long* tail_count, long long tail_cap, long long tail_base,
-                                          int chunk_shift, int* tail_fill, int* overflow, int total, int ln, TailExt* e,
-                                          int64_t& pos) {
-    const int chunk = 1 << chunk_shift;
+// `e` = the wave's slot in LDS (one wave reads and writes it, in program order); chunk = 1 << tail_shift.
+__device__ __forceinline__ bool tail_take(const CandList& l, int total, int ln, TailExt* e, int64_t& pos) {
+    const int chunk = 1 << l.tail_shift;
     int left = e->left;
     long long p = e->pos;
     if (left < 0) return false;
     if (total > chunk) {  // (only the block-at-a-time emitter asks for more than 64 at once: rerun with larger buffers)
-        if (ln == 0) { atomicOr(overflow, 2); e->left = -1; }
+        if (ln == 0) { atomicOr(l.overflow, 2); e->left = -1; }
         return false;
     }
     if (total > left) {
         // close the current chunk (its fill level), take the next one
-        if (ln == 0 && e->have) tail_fill[(p - 1 - tail_base) >> chunk_shift] = chunk - left;
+        if (ln == 0 && e->have) l.tail_fill[(p - 1 - (long long)l.tail_base) >> l.tail_shift] = chunk - left;
         unsigned long long base = 0;
-        if (ln == 0) base = atomicAdd(tail_count, (unsigned long long)chunk);
+        if (ln == 0) base = atomicAdd(l.tail_count, (unsigned long long)chunk);
         base = __shfl(base, 0);
-        if ((long long)(base + chunk) > tail_cap) {
-            if (ln == 0) { atomicOr(overflow, 2); e->left = -1; e->have = 0; }
+        if ((long long)(base + chunk) > l.tail_cap) {
+            if (ln == 0) { atomicOr(l.overflow, 2); e->left = -1; e->have = 0; }
             return false;
         }
-        p = tail_base + (long long)base;
+        p = (long long)l.tail_base + (long long)base;
         left = chunk;
     }
     pos = p;
@@ -59,8 +71,9 @@ __device__ __forceinline__ bool tail_take(unsigned long long* tail_count, long l
 }
 
 // at the end of the kernel: the fill level of the wave's last chunk
-__device__ __forceinline__ void tail_close(long long tail_base, int chunk_shift, int* tail_fill, int ln, TailExt* e) {
-    if (ln == 0 && e->have && e->left >= 0) tail_fill[(e->pos - 1 - tail_base) >> chunk_shift] = (1 << chunk_shift) - e->left;
+__device__ __forceinline__ void tail_close(const CandList& l, int ln, TailExt* e) {
+    if (ln == 0 && e->have && e->left >= 0)
+        l.tail_fill[(e->pos - 1 - (long long)l.tail_base) >> l.tail_shift] = (1 << l.tail_shift) - e->left;
 }
 
 // chunk size of a launch (a power of two, as a shift): large enough that the atomics vanish, small enough that every

@@ -6,6 +6,19 @@
 
 namespace vscmi {
 
+// Scratch of the radix sorts (sortpairs.hip): two key and two value ping-pong buffers + the sort's own temporary.
+struct SortScratch {
+    DevBuf w0, w1, w2, w3, tmp;
+    void release() { w0.release(); w1.release(); w2.release(); w3.release(); tmp.release(); }
+};
+// A hit list on the device: (row, ref, score) in three parallel arrays.
+struct HitView { int32_t* i; int32_t* j; float* s; };
+struct ConstHitView {
+    const int32_t* i; const int32_t* j; const float* s;
+    ConstHitView(const int32_t* i_, const int32_t* j_, const float* s_) : i(i_), j(j_), s(s_) {}
+    ConstHitView(const HitView& v) : i(v.i), j(v.j), s(v.s) {}
+};
+
 struct SimThreshArgs {
     const float* Q; const float* R; int dpad; int nq; int i0; int nr; int tq; int tr;
     const float* radius; int32_t* out_i; int32_t* out_j; float* out_s;
@@ -18,14 +31,11 @@ struct SimF16Args {
     const float* qn; const float* rn;      // per-row upper bounds of the L2 norm (+inf: row not representable)
     int dpadh; int nq; int i0; int nr; int tq; int tr;
     float c1, c2, c3;                      // |fp16 score - exact score| <= c1*nq*nr + c2*(nq+nr) + c3
-    const float* radius; int32_t* out_i; int32_t* out_j;
+    const float* radius;
     // k-NN mode: per-row thresholds (indexed like qn; the test becomes fp16 score + bound >= row_thr[row]);
     // nullptr = thresholded search against *radius
     const float* row_thr;
-    // candidate list = one private segment of seg_cap entries per wave of the launch (8 per workgroup)
-    // + a shared tail (atomic counter) for waves whose segment is full
-    int seg_cap; int* seg_count; int64_t tail_base; long long tail_cap; int tail_shift; int* tail_fill; unsigned long long* tail_count;
-    int* overflow;
+    CandList list;                         // where the candidates go (cand_list.h)
 };
 // panel-stationary fp16 pre-filter (sim_f16p.hip; dpadh <= 512): the query side is the natural fp16 image, the
 // reference side the FRAGMENT-MAJOR image written by launch_pack_half_frag (layout.hip)
@@ -40,9 +50,7 @@ struct SimF16PArgs {
     int* next_slice;                       // [npanel] slices handed out so far (zeroed by the launcher)
     float c1, c2, c3;
     const float* radius; const float* row_thr;  // as in SimF16Args
-    int32_t* out_i; int32_t* out_j;
-    int seg_cap; int* seg_count; int64_t tail_base; long long tail_cap; int tail_shift; int* tail_fill; unsigned long long* tail_count;
-    int* overflow;
+    CandList list;
 };
 // panel-stationary INT8 pre-filter (sim_i8p.hip; dims <= 1024): the query side is the launch's own int8 image with one
 // scale per 128-row panel (quant_query_panels), the reference side the fragment-major int8 image + per-row meta of
@@ -71,21 +79,17 @@ struct SimI8PArgs {
     int pair;                              // 1: work items of TWO panels, wave tiles of 256 rows x 32 columns (sim_i8p_pairs)
     float c_acc;                           // rounding of the exact fp32 chain per |q||r|
     const float* radius; const float* row_thr;  // as in SimF16Args (row_thr indexed by POSITION inside the launch)
-    int32_t* out_i; int32_t* out_j;
-    int seg_cap; int* seg_count; int64_t tail_base; long long tail_cap; int tail_shift; int* tail_fill; unsigned long long* tail_count;
-    int* overflow;
+    CandList list;
 };
 struct RescoreArgs {
     const float* Q; const float* R; int dpad;  // packed fp32 images (exact arithmetic contract)
-    const int32_t* cand_i; const int32_t* cand_j; int n_seg; int seg_cap; const int* seg_count;
-    int64_t tail_base; long long tail_cap; unsigned long long* tail_count;  // reset to 0 after the pass
-    int tail_shift; const int* tail_fill;  // the tail is handed out in chunks of 1 << tail_shift entries, each with a fill level
+    CandList list;  // the pre-filter launch's candidates (cand_list.h); tail_count is reset to 0 after the pass
     // the int8 kernel hands over POSITIONS inside its launch when the launch's rows were permuted (sorted by threshold
     // or by scale): row = perm_i0 + perm[position - perm_i0].  nullptr: the list holds rows
     const int32_t* perm; int perm_i0;
     unsigned long long* n_cand_total;      // statistics
     const float* radius; int32_t* out_i; int32_t* out_j; float* out_s;
-    unsigned long long* counter; long long cap; int* overflow;
+    unsigned long long* counter; long long cap;  // (a full kept-hit list sets bit 0 of *list.overflow)
     const float* row_thr;  // k-NN mode: keep score >= row_thr[global row] (nullptr: score > *radius)
     // the launch searched the reference rows [j0, j0 + nr): the kernels' images were handed over from row j0 on, the
     // candidate list holds refs RELATIVE to it (cand_compact / the segment-wise exact stage add j0 back)
@@ -165,36 +169,30 @@ int launch_quant_query_panels(const float*, int, int, int, void*, int, float4*, 
 int launch_row_absmax(const float*, int, int, const ExcludedDims&, float*, hipStream_t);
 int launch_row_bias_thresholds(const float*, int, int, const float*, const float*, const ExcludedDims&, const float*, const float*, float*,
                                hipStream_t);
-int sort_rows_by_threshold(const float*, int64_t, DevBuf&, DevBuf&, DevBuf&, DevBuf&, DevBuf&, const int32_t**, hipStream_t);
-int argsort_scores_desc(const float*, int64_t, DevBuf&, DevBuf&, DevBuf&, DevBuf&, DevBuf&, const int32_t**, hipStream_t);
+int sort_rows_by_threshold(const float*, int64_t, SortScratch&, const int32_t**, hipStream_t);
+int argsort_scores_desc(const float*, int64_t, SortScratch&, const int32_t**, hipStream_t);
 int launch_ctl_init(SelectCtl*, float, hipStream_t);
-int launch_filter_hits(const int32_t*, const int32_t*, const float*, long long, float, int32_t*, int32_t*, float*, unsigned long long*,
-                       hipStream_t);
+int launch_filter_hits(ConstHitView, long long, float, HitView, unsigned long long*, hipStream_t);
 int launch_score_hist(const float*, long long, const long long*, int, long long*, hipStream_t);
 int launch_score_pick(const long long*, long long*, int, hipStream_t);
 int launch_merge_topk(const float*, const long long*, long long, int, int, float*, long long*, hipStream_t);
-int sort_rows_by_threshold_then_scale(const float*, const float*, int64_t, int, DevBuf&, DevBuf&, DevBuf&, DevBuf&, DevBuf&,
-                                      const int32_t**, hipStream_t);
+int sort_rows_by_threshold_then_scale(const float*, const float*, int64_t, int, SortScratch&, const int32_t**, hipStream_t);
 int launch_pack_half_frag(const float*, int64_t, int, _Float16*, float*, int64_t, int64_t, int, hipStream_t);
 int launch_pack_half(const float*, int64_t, int, _Float16*, float*, int64_t, int, hipStream_t);
 int launch_sim_knn(const SimKnnArgs&, hipStream_t);
 int launch_knn_merge(const KnnMergeArgs&, hipStream_t);
-int knn_from_hits(const int32_t*, const int32_t*, const float*, int64_t, int64_t, int, DevBuf&, DevBuf&, DevBuf&,
-                  DevBuf&, DevBuf&, float*, int64_t*, hipStream_t);
+int knn_from_hits(ConstHitView, int64_t, int64_t, int, SortScratch&, float*, int64_t*, hipStream_t);
 int launch_knn_row_thr(const float*, int64_t, int, float*, int64_t, hipStream_t);
-int launch_knn_seed_hits(const float*, const int64_t*, int64_t, int, int32_t*, int32_t*, float*, unsigned long long*, hipStream_t);
+int launch_knn_seed_hits(const float*, const int64_t*, int64_t, int, HitView, unsigned long long*, hipStream_t);
 int launch_score_matrix(const ScoreMatArgs&, hipStream_t);
 int launch_matrix_thresh(const MatThreshArgs&, hipStream_t);
 int launch_matrix_knn(const MatKnnArgs&, hipStream_t);
 int set_thresh_kernel_attrs();
-int enqueue_rethreshold(SelectCtl*, int32_t*, int32_t*, float*, int32_t*, int32_t*, float*, unsigned long long, hipStream_t);
-int sort_hits_topk(const int32_t*, const int32_t*, const float*, int64_t, int64_t, int64_t, int64_t, DevBuf&, DevBuf&,
-                   DevBuf&, DevBuf&, DevBuf&, int32_t*, int32_t*, float*, int, int64_t*, hipStream_t);
-int sort_hits_rowcol(const int32_t*, const int32_t*, const float*, int64_t, DevBuf&, DevBuf&, DevBuf&, DevBuf&,
-                     DevBuf&, int32_t*, int32_t*, float*, int, hipStream_t);
+int enqueue_rethreshold(SelectCtl*, HitView, HitView, unsigned long long, hipStream_t);
+int sort_hits_topk(ConstHitView, int64_t, int64_t, int64_t, int64_t, SortScratch&, HitView, int, int64_t*, hipStream_t);
+int sort_hits_rowcol(ConstHitView, int64_t, SortScratch&, HitView, int, hipStream_t);
 int pair_max_device(const int32_t*, const int32_t*, const float*, int64_t, const int32_t*, const int32_t*, int64_t, int64_t,
-                    DevBuf&, DevBuf&, DevBuf&, DevBuf&, DevBuf&, DevBuf&, int32_t*, int32_t*, float*, int64_t*,
-                    int64_t, int64_t*, hipStream_t);
+                    SortScratch&, DevBuf&, int32_t*, int32_t*, float*, int64_t*, int64_t, int64_t*, hipStream_t);
 int launch_pack_rows(const float*, int64_t, int, float*, int64_t, int, hipStream_t);
 int launch_row_normalize(const float*, int64_t, int, float*, hipStream_t);
 size_t tn_state_bytes_host(int, int, int, int idx_bytes = 2);

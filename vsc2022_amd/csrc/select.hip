@@ -186,16 +186,15 @@ int launch_ctl_init(SelectCtl* ctl, float radius, hipStream_t stream) {
 }
 
 // Enqueue one "if n > 2K: radius <- (K+1)-th best; keep score > radius" round.
-int enqueue_rethreshold(SelectCtl* ctl, int32_t* ai, int32_t* aj, float* as, int32_t* bi, int32_t* bj,
-                        float* bs, unsigned long long K, hipStream_t stream) {
+int enqueue_rethreshold(SelectCtl* ctl, HitView a, HitView b, unsigned long long K, hipStream_t stream) {
     constexpr int GRID = 1024;
     hipLaunchKernelGGL(select_begin_kernel, dim3(1), dim3(256), 0, stream, ctl, 2 * K, K);
     for (int shift = 24; shift >= 0; shift -= 8) {
-        hipLaunchKernelGGL(select_hist_kernel, dim3(GRID), dim3(256), 0, stream, ctl, as, shift);
+        hipLaunchKernelGGL(select_hist_kernel, dim3(GRID), dim3(256), 0, stream, ctl, a.s, shift);
         hipLaunchKernelGGL(select_pick_kernel, dim3(1), dim3(256), 0, stream, ctl, shift);
     }
-    hipLaunchKernelGGL(select_compact_kernel, dim3(GRID), dim3(256), 0, stream, ctl, ai, aj, as, bi, bj, bs);
-    hipLaunchKernelGGL(select_copyback_kernel, dim3(GRID), dim3(256), 0, stream, ctl, bi, bj, bs, ai, aj, as);
+    hipLaunchKernelGGL(select_compact_kernel, dim3(GRID), dim3(256), 0, stream, ctl, a.i, a.j, a.s, b.i, b.j, b.s);
+    hipLaunchKernelGGL(select_copyback_kernel, dim3(GRID), dim3(256), 0, stream, ctl, b.i, b.j, b.s, a.i, a.j, a.s);
     hipLaunchKernelGGL(select_end_kernel, dim3(1), dim3(1), 0, stream, ctl);
     VSC_HIP(hipGetLastError());
     return VSC_OK;
@@ -329,12 +328,11 @@ __global__ __launch_bounds__(256) void filter_hits_kernel(const int32_t* __restr
     }
 }
 
-int launch_filter_hits(const int32_t* ai, const int32_t* aj, const float* as, long long n, float radius, int32_t* bi, int32_t* bj,
-                       float* bs, unsigned long long* n_out, hipStream_t stream) {
+int launch_filter_hits(ConstHitView a, long long n, float radius, HitView b, unsigned long long* n_out, hipStream_t stream) {
     VSC_HIP(hipMemsetAsync(n_out, 0, sizeof(unsigned long long), stream));
     if (n <= 0) return VSC_OK;
     const int grid = (int)std::min<long long>(1024, (n + 2047) / 2048);
-    hipLaunchKernelGGL(filter_hits_kernel, dim3(grid), dim3(256), 0, stream, ai, aj, as, n, radius, bi, bj, bs, n_out);
+    hipLaunchKernelGGL(filter_hits_kernel, dim3(grid), dim3(256), 0, stream, a.i, a.j, a.s, n, radius, b.i, b.j, b.s, n_out);
     VSC_HIP(hipGetLastError());
     return VSC_OK;
 }

@@ -335,13 +335,13 @@ __device__ __forceinline__ void emit_candidates(const SimF16Args& a, bool all, f
                     count += total;
                 } else {
                     // segment full (candidates are not spread evenly): the wave's chunk of the shared tail
-                    if (!tail_take(a.tail_count, a.tail_cap, a.tail_base, a.tail_shift, a.tail_fill, a.overflow, total, lane, ext, pos))
+                    if (!tail_take(a.list, total, lane, ext, pos))
                         continue;
                 }
                 if ((ok >> lane) & 1ull) {
                     pos += __popcll(ok & ((1ull << lane) - 1));
-                    a.out_i[pos] = a.i0 + i;
-                    a.out_j[pos] = j;
+                    a.list.i[pos] = a.i0 + i;
+                    a.list.j[pos] = j;
                 }
             }
         }
@@ -365,14 +365,14 @@ __global__ __launch_bounds__(512, 1) void sim_f16_kernel(SimF16Args a) {
     const int64_t lstride = gridDim.x >> 3;  // gridDim.x is a multiple of 8
     // this wave's private segment of the candidate list
     const int seg = blockIdx.x * 8 + __builtin_amdgcn_readfirstlane(wave);
-    const int64_t seg_base = (int64_t)seg * a.seg_cap;
+    const int64_t seg_base = (int64_t)seg * a.list.seg_cap;
     int count = 0;
     tail_init(&tail_sh[wave], lane);
     int64_t local = blockIdx.x >> 3;
     int tqi;
     int64_t tri;
     if (!raster(xcd, local, a.tq, a.tr, tqi, tri)) {
-        if (lane == 0) a.seg_count[seg] = 0;
+        if (lane == 0) a.list.seg_count[seg] = 0;
         return;
     }
     TileStream st;
@@ -431,7 +431,7 @@ __global__ __launch_bounds__(512, 1) void sim_f16_kernel(SimF16Args a) {
             count += mx == 12345.678f;  // keeps the accumulators alive; garbage results are not emitted
         } else if (all || __any(ROWTHR ? any_blk : mx > thr))
             emit_candidates<ROWTHR>(a, all, thr, thrb, rt, eps, tqi * BM + wr * 128, wr * 128,
-                                    tri * BN + wc * 64, acc, bm, lane, seg_base, a.seg_cap, count, &tail_sh[wave]);
+                                    tri * BN + wc * 64, acc, bm, lane, seg_base, a.list.seg_cap, count, &tail_sh[wave]);
         if (!has_next) break;
         local += lstride;
         tqi = ntq;
@@ -439,8 +439,8 @@ __global__ __launch_bounds__(512, 1) void sim_f16_kernel(SimF16Args a) {
     }
     // the stream fetched two K-tiles past its end: let them land before the LDS is handed back
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    tail_close(a.tail_base, a.tail_shift, a.tail_fill, lane, &tail_sh[wave]);
-    if (lane == 0) a.seg_count[seg] = count;
+    tail_close(a.list, lane, &tail_sh[wave]);
+    if (lane == 0) a.list.seg_count[seg] = count;
 }
 
 // grid of a launch: one persistent workgroup per CU (fewer for tiny problems); 8 segments each
@@ -504,7 +504,7 @@ __device__ __forceinline__ void flush_hits(const RescoreArgs& a, WaveHits& buf, 
     if (lane == 0) base = atomicAdd(a.counter, (unsigned long long)pend);
     base = __shfl(base, 0);
     if ((long long)(base + pend) > a.cap) {
-        if (lane == 0) atomicOr(a.overflow, 1);
+        if (lane == 0) atomicOr(a.list.overflow, 1);
     } else if (lane < pend) {
         a.out_i[base + lane] = buf.i[lane];
         a.out_j[base + lane] = buf.j[lane];
@@ -612,7 +612,7 @@ __global__ __launch_bounds__(256) void rescore_kernel(RescoreArgs a) {
     // After an overflow the candidate list has holes (a wave whose tail reservation did not fit skipped its
     // writes but the tail counter moved on): the host reruns the search with larger buffers, so do nothing
     // rather than chase unwritten (row, ref) pairs through memory.
-    if (*a.overflow) return;
+    if (*a.list.overflow) return;
     __shared__ WaveHits wave_hits[4];
     WaveHits& buf = wave_hits[threadIdx.x >> 6];
     int pend = 0;
@@ -622,18 +622,18 @@ __global__ __launch_bounds__(256) void rescore_kernel(RescoreArgs a) {
     // better and keep more loads in flight)
     {
         const int seg = blockIdx.x / RESCORE_SHARE, part = blockIdx.x % RESCORE_SHARE;
-        const int n = min(a.seg_count[seg], a.seg_cap);
+        const int n = min(a.list.seg_count[seg], a.list.seg_cap);
         if (part == 0) seen += (unsigned long long)n;
-        rescore_list<SRC>(a, radius, a.cand_i + (int64_t)seg * a.seg_cap, a.cand_j + (int64_t)seg * a.seg_cap, n,
+        rescore_list<SRC>(a, radius, a.list.i + (int64_t)seg * a.list.seg_cap, a.list.j + (int64_t)seg * a.list.seg_cap, n,
                      part * 256 + threadIdx.x, 256 * RESCORE_SHARE, buf, pend);
     }
     // shared tail (normally empty)
-    const unsigned long long nt_all = *a.tail_count;
-    const long long nt = nt_all < (unsigned long long)a.tail_cap ? (long long)nt_all : a.tail_cap;
+    const unsigned long long nt_all = *a.list.tail_count;
+    const long long nt = nt_all < (unsigned long long)a.list.tail_cap ? (long long)nt_all : a.list.tail_cap;
     if (nt > 0) {
-        rescore_list<SRC>(a, radius, a.cand_i + a.tail_base, a.cand_j + a.tail_base, nt,
-                     (long long)blockIdx.x * 256 + threadIdx.x, (long long)gridDim.x * 256, buf, pend, a.tail_fill,
-                     a.tail_shift);
+        rescore_list<SRC>(a, radius, a.list.i + a.list.tail_base, a.list.j + a.list.tail_base, nt,
+                     (long long)blockIdx.x * 256 + threadIdx.x, (long long)gridDim.x * 256, buf, pend, a.list.tail_fill,
+                     a.list.tail_shift);
         if (blockIdx.x == 0) seen += (unsigned long long)nt;
     }
     flush_hits(a, buf, pend);
@@ -651,21 +651,21 @@ __global__ void tail_reset_kernel(unsigned long long* tail_count) { *tail_count 
 __global__ __launch_bounds__(256) void cand_compact_kernel(RescoreArgs a, uint32_t* __restrict__ key_j,
                                                            uint32_t* __restrict__ val_i, unsigned long long* n_out) {
     __shared__ unsigned long long base_sh;
-    if (*a.overflow) return;
+    if (*a.list.overflow) return;
     const int b = blockIdx.x;
     const int32_t *ci, *cj;
     int n;
-    if (b < a.n_seg) {
-        n = min(a.seg_count[b], a.seg_cap);
-        ci = a.cand_i + (int64_t)b * a.seg_cap;
-        cj = a.cand_j + (int64_t)b * a.seg_cap;
+    if (b < a.list.n_seg) {
+        n = min(a.list.seg_count[b], a.list.seg_cap);
+        ci = a.list.i + (int64_t)b * a.list.seg_cap;
+        cj = a.list.j + (int64_t)b * a.list.seg_cap;
     } else {
-        const long long chunk = b - a.n_seg;
-        const unsigned long long nt = *a.tail_count;
-        if ((unsigned long long)(chunk << a.tail_shift) >= nt || (long long)nt > a.tail_cap) return;
-        n = a.tail_fill[chunk];
-        ci = a.cand_i + a.tail_base + (chunk << a.tail_shift);
-        cj = a.cand_j + a.tail_base + (chunk << a.tail_shift);
+        const long long chunk = b - a.list.n_seg;
+        const unsigned long long nt = *a.list.tail_count;
+        if ((unsigned long long)(chunk << a.list.tail_shift) >= nt || (long long)nt > a.list.tail_cap) return;
+        n = a.list.tail_fill[chunk];
+        ci = a.list.i + a.list.tail_base + (chunk << a.list.tail_shift);
+        cj = a.list.j + a.list.tail_base + (chunk << a.list.tail_shift);
     }
     if (n <= 0) return;
     if (threadIdx.x == 0) base_sh = atomicAdd(n_out, (unsigned long long)n);
@@ -771,7 +771,7 @@ template <int SRC>
 __global__ __launch_bounds__(256) void rescore_dense_kernel(RescoreArgs a, const uint32_t* __restrict__ sj,
                                                             const uint32_t* __restrict__ si, long long n,
                                                             const unsigned long long* __restrict__ n_dev) {
-    if (*a.overflow) return;
+    if (*a.list.overflow) return;
     if (n_dev) n = (long long)*n_dev;
     __shared__ WaveHits wave_hits[4];
     WaveHits& buf = wave_hits[threadIdx.x >> 6];
@@ -791,12 +791,12 @@ __global__ __launch_bounds__(256) void rescore_dense_kernel(RescoreArgs a, const
 __global__ __launch_bounds__(1024) void cand_count_kernel(RescoreArgs a, int n_chunks_max, unsigned long long* n_out) {
     __shared__ unsigned long long red[16];
     unsigned long long s = 0;
-    if (!*a.overflow) {
-        for (int b = threadIdx.x; b < a.n_seg; b += 1024) s += (unsigned long long)max(0, min(a.seg_count[b], a.seg_cap));
-        const unsigned long long nt = *a.tail_count;
-        if ((long long)nt <= a.tail_cap) {
-            const long long used = (long long)((nt + (1ull << a.tail_shift) - 1) >> a.tail_shift);
-            for (long long c = threadIdx.x; c < used && c < n_chunks_max; c += 1024) s += (unsigned long long)max(0, a.tail_fill[c]);
+    if (!*a.list.overflow) {
+        for (int b = threadIdx.x; b < a.list.n_seg; b += 1024) s += (unsigned long long)max(0, min(a.list.seg_count[b], a.list.seg_cap));
+        const unsigned long long nt = *a.list.tail_count;
+        if ((long long)nt <= a.list.tail_cap) {
+            const long long used = (long long)((nt + (1ull << a.list.tail_shift) - 1) >> a.list.tail_shift);
+            for (long long c = threadIdx.x; c < used && c < n_chunks_max; c += 1024) s += (unsigned long long)max(0, a.list.tail_fill[c]);
         }
     }
 #pragma unroll
@@ -819,7 +819,7 @@ int launch_cand_count(const RescoreArgs& a, int n_chunks_max, unsigned long long
 int launch_cand_compact(const RescoreArgs& a, int n_chunks_max, uint32_t* key_j, uint32_t* val_i, unsigned long long* n_out,
                         hipStream_t stream) {
     VSC_HIP(hipMemsetAsync(n_out, 0, sizeof(unsigned long long), stream));
-    hipLaunchKernelGGL(cand_compact_kernel, dim3((unsigned)(a.n_seg + n_chunks_max)), dim3(256), 0, stream, a, key_j, val_i, n_out);
+    hipLaunchKernelGGL(cand_compact_kernel, dim3((unsigned)(a.list.n_seg + n_chunks_max)), dim3(256), 0, stream, a, key_j, val_i, n_out);
     VSC_HIP(hipGetLastError());
     return VSC_OK;
 }
@@ -832,18 +832,18 @@ int launch_rescore_dense(const RescoreArgs& a, const uint32_t* sj, const uint32_
         else if (a.rsrc == 1) hipLaunchKernelGGL(rescore_dense_kernel<1>, dim3(grid), dim3(256), 0, stream, a, sj, si, n, n_dev);
         else hipLaunchKernelGGL(rescore_dense_kernel<2>, dim3(grid), dim3(256), 0, stream, a, sj, si, n, n_dev);
     }
-    hipLaunchKernelGGL(tail_reset_kernel, dim3(1), dim3(1), 0, stream, a.tail_count);
+    hipLaunchKernelGGL(tail_reset_kernel, dim3(1), dim3(1), 0, stream, a.list.tail_count);
     VSC_HIP(hipGetLastError());
     return VSC_OK;
 }
 
 int launch_rescore(const RescoreArgs& a, hipStream_t stream) {
-    if (a.n_seg <= 0) return VSC_OK;
-    const dim3 grid((unsigned)a.n_seg * RESCORE_SHARE);
+    if (a.list.n_seg <= 0) return VSC_OK;
+    const dim3 grid((unsigned)a.list.n_seg * RESCORE_SHARE);
     if (a.rsrc == 0) hipLaunchKernelGGL(rescore_kernel<0>, grid, dim3(256), 0, stream, a);
     else if (a.rsrc == 1) hipLaunchKernelGGL(rescore_kernel<1>, grid, dim3(256), 0, stream, a);
     else hipLaunchKernelGGL(rescore_kernel<2>, grid, dim3(256), 0, stream, a);
-    hipLaunchKernelGGL(tail_reset_kernel, dim3(1), dim3(1), 0, stream, a.tail_count);
+    hipLaunchKernelGGL(tail_reset_kernel, dim3(1), dim3(1), 0, stream, a.list.tail_count);
     VSC_HIP(hipGetLastError());
     return VSC_OK;
 }

@@ -143,18 +143,18 @@ __device__ __forceinline__ void emit_candidates(const SimF16PArgs& a, const bool
                 if (ok == 0ull) continue;
                 const int total = __popcll(ok);
                 int64_t pos;
-                if (count + total <= a.seg_cap) {
+                if (count + total <= a.list.seg_cap) {
                     pos = seg_base + count;
                     count += total;
                 } else {
                     // segment full (candidates are not spread evenly): the wave's chunk of the shared tail
-                    if (!tail_take(a.tail_count, a.tail_cap, a.tail_base, a.tail_shift, a.tail_fill, a.overflow, total, ln, ext, pos))
+                    if (!tail_take(a.list, total, ln, ext, pos))
                         continue;
                 }
                 if (mine) {
                     pos += __builtin_amdgcn_mbcnt_hi((unsigned)(ok >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ok, 0u));
-                    a.out_i[pos] = a.i0 + i;
-                    a.out_j[pos] = j;
+                    a.list.i[pos] = a.i0 + i;
+                    a.list.j[pos] = j;
                 }
             }
         }
@@ -208,12 +208,12 @@ __device__ __forceinline__ void emit_candidates_blk(const SimF16PArgs& a, const 
             }
             if (total == 0) continue;
             int64_t pos;
-            if (count + total <= a.seg_cap) {
+            if (count + total <= a.list.seg_cap) {
                 pos = seg_base + count;
                 count += total;
             } else {
                 // segment full (candidates are not spread evenly): the wave's chunk of the shared tail
-                if (!tail_take(a.tail_count, a.tail_cap, a.tail_base, a.tail_shift, a.tail_fill, a.overflow, total, ln, ext, pos))
+                if (!tail_take(a.list, total, ln, ext, pos))
                     continue;
             }
             pos += before;
@@ -221,8 +221,8 @@ __device__ __forceinline__ void emit_candidates_blk(const SimF16PArgs& a, const 
             while (mask) {
                 const int r = __ffs(mask) - 1;
                 mask &= mask - 1;
-                a.out_i[pos] = ibase + (r & 3) + 8 * (r >> 2);
-                a.out_j[pos] = j;
+                a.list.i[pos] = ibase + (r & 3) + 8 * (r >> 2);
+                a.list.j[pos] = j;
                 ++pos;
             }
         }
@@ -295,14 +295,14 @@ __global__ __launch_bounds__(512) void sim_f16p_kernel(SimF16PArgs a) {
     }
     const float radius = ROWTHR ? 0.0f : *a.radius;
     const int seg = blockIdx.x * 8 + wave;  // this wave's private segment of the candidate list
-    const int64_t seg_base = (int64_t)seg * a.seg_cap;
+    const int64_t seg_base = (int64_t)seg * a.list.seg_cap;
     int count = 0;
     tail_init(&tail_sh[wave], lane);  // the wave's chunk of the shared tail once its segment is full (cand_list.h)
     // the wave's segment of the two candidate arrays as buffer resources (emit_candidates_seg)
     const __amdgpu_buffer_rsrc_t rs_ci = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)uniform_ptr(reinterpret_cast<const char*>(a.out_i + seg_base)), 0, a.seg_cap * 4, 0x00020000);
+        (void*)uniform_ptr(reinterpret_cast<const char*>(a.list.i + seg_base)), 0, a.list.seg_cap * 4, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_cj = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)uniform_ptr(reinterpret_cast<const char*>(a.out_j + seg_base)), 0, a.seg_cap * 4, 0x00020000);
+        (void*)uniform_ptr(reinterpret_cast<const char*>(a.list.j + seg_base)), 0, a.list.seg_cap * 4, 0x00020000);
     const int nslice = (a.nsteps + a.slice - 1) / a.slice;
     int cur_panel = -1;
     float nq_max = 0.f;
@@ -316,7 +316,7 @@ __global__ __launch_bounds__(512) void sim_f16p_kernel(SimF16PArgs a) {
             // a launch whose candidate list has overflowed is lost (the host reruns it with larger buffers): stop
             // taking work
 #ifndef VSC_NO_LOST_CHECK
-            const bool lost = __hip_atomic_load(a.overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+            const bool lost = __hip_atomic_load(a.list.overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
 #else
             const bool lost = false;
 #endif
@@ -437,7 +437,7 @@ __global__ __launch_bounds__(512) void sim_f16p_kernel(SimF16PArgs a) {
             }
             if (__any(any_blk)) {
                 const bool interior = panel * PR + PR <= a.nq && col0 + 64 <= a.nr;
-                if (VSC_F16P_EMIT == 3 && !ROWTHR && interior && !all[0] && !all[1] && count + 8192 <= a.seg_cap)
+                if (VSC_F16P_EMIT == 3 && !ROWTHR && interior && !all[0] && !all[1] && count + 8192 <= a.list.seg_cap)
                     emit_candidates_seg(a, thr, panel * PR, col0, acc, bm, rs_ci, rs_cj, count);
                 else if (VSC_F16P_EMIT == 2 || (VSC_F16P_EMIT == 0 && !ROWTHR))
                     emit_candidates_blk<ROWTHR>(a, all, thr, eps, rt_sh, rtmin, panel * PR, col0, interior, acc, bm,
@@ -448,8 +448,8 @@ __global__ __launch_bounds__(512) void sim_f16p_kernel(SimF16PArgs a) {
             }
         }
     }
-    tail_close(a.tail_base, a.tail_shift, a.tail_fill, lane, &tail_sh[wave]);
-    if (lane == 0) a.seg_count[seg] = count;
+    tail_close(a.list, lane, &tail_sh[wave]);
+    if (lane == 0) a.list.seg_count[seg] = count;
 }
 
 // Work split of one launch: slices (in col-steps) such that every workgroup sees >= ~16 items when the
@@ -487,7 +487,7 @@ static int launch_nkc(const SimF16PArgs& a, int grid, hipStream_t stream) {
 int launch_sim_f16p(const SimF16PArgs& a, int grid, hipStream_t stream) {
     if (grid <= 0 || a.npanel <= 0 || a.nsteps <= 0) {
         // nothing to search: the caller's exact stage must see empty segments, not stale fill levels
-        if (grid > 0) VSC_HIP(hipMemsetAsync(a.seg_count, 0, (size_t)grid * 8 * sizeof(int), stream));
+        if (grid > 0) VSC_HIP(hipMemsetAsync(a.list.seg_count, 0, (size_t)a.list.n_seg * sizeof(int), stream));
         return VSC_OK;
     }
     VSC_HIP(hipMemsetAsync(a.next_slice, 0, (size_t)a.npanel * sizeof(int), stream));

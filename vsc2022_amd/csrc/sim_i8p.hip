@@ -240,18 +240,18 @@ __device__ __forceinline__ void emit_candidates(const SimI8PArgs& a, const int (
                 if (ok == 0ull) continue;
                 const int total = __popcll(ok);
                 int64_t pos;
-                if (count + total <= a.seg_cap) {
+                if (count + total <= a.list.seg_cap) {
                     pos = seg_base + count;
                     count += total;
                 } else {
                     // segment full (candidates are not spread evenly): the wave's chunk of the shared tail
-                    if (!tail_take(a.tail_count, a.tail_cap, a.tail_base, a.tail_shift, a.tail_fill, a.overflow, total, ln, ext, pos))
+                    if (!tail_take(a.list, total, ln, ext, pos))
                         continue;
                 }
                 if (mine) {
                     pos += __builtin_amdgcn_mbcnt_hi((unsigned)(ok >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ok, 0u));
-                    a.out_i[pos] = a.i0 + i;  // (a position when the launch's rows are permuted: the exact stage maps it back)
-                    a.out_j[pos] = j;
+                    a.list.i[pos] = a.i0 + i;  // (a position when the launch's rows are permuted: the exact stage maps it back)
+                    a.list.j[pos] = j;
                 }
             }
         }
@@ -341,13 +341,13 @@ __global__ __launch_bounds__(512) void sim_i8p_kernel(SimI8PArgs a) {
     }
     const float radius = ROWTHR ? 0.0f : *a.radius;
     const int seg = blockIdx.x * 8 + wave;  // this wave's private segment of the candidate list
-    const int64_t seg_base = (int64_t)seg * a.seg_cap;
+    const int64_t seg_base = (int64_t)seg * a.list.seg_cap;
     int count = 0;
     tail_init(&tail_sh[wave], lane);  // the wave's chunk of the shared tail once its segment is full (cand_list.h)
     const __amdgpu_buffer_rsrc_t rs_ci = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)uniform_ptr(reinterpret_cast<const char*>(a.out_i + seg_base)), 0, a.seg_cap * 4, 0x00020000);
+        (void*)uniform_ptr(reinterpret_cast<const char*>(a.list.i + seg_base)), 0, a.list.seg_cap * 4, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_cj = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)uniform_ptr(reinterpret_cast<const char*>(a.out_j + seg_base)), 0, a.seg_cap * 4, 0x00020000);
+        (void*)uniform_ptr(reinterpret_cast<const char*>(a.list.j + seg_base)), 0, a.list.seg_cap * 4, 0x00020000);
     // work items: (slice of a.slice 512-column col-steps, panel of PRW rows); a.npanel counts 128-row panels
     const int npan = (a.npanel + HALVES - 1) / HALVES;
     const int nslice = (a.nsteps + a.slice - 1) / a.slice;
@@ -369,7 +369,7 @@ __global__ __launch_bounds__(512) void sim_i8p_kernel(SimI8PArgs a) {
             // a launch whose candidate list has overflowed is lost (the host reruns the batch on the fp16 kernel or
             // with larger buffers): stop taking work instead of pushing billions of candidates through the tail's
             // one atomic counter (an 8-bit bound that is too loose for the data can pass most of the matrix)
-            const bool lost = __hip_atomic_load(a.overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+            const bool lost = __hip_atomic_load(a.list.overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
             if (a.order == 1 && !lost) {
                 // slice-major: items (slice, panel) in one global order -- every workgroup of the chip is inside
                 // the same few MB of the reference image, each XCD fetches a slice once; the price is a panel load
@@ -544,7 +544,7 @@ __global__ __launch_bounds__(512) void sim_i8p_kernel(SimI8PArgs a) {
 #endif
             if (VSC_I8P_ABLATE == 0 && __any(any_col)) {
                 const bool interior = panel * PRW + PRW <= a.nq && col0 + WCOLS <= a.nr;
-                if (interior && count + 8192 <= a.seg_cap) {
+                if (interior && count + 8192 <= a.list.seg_cap) {
                     emit_candidates_seg<ROWTHR, MB, CB, 0>(a, tc[0], cm[0], rt16, eps_own[0], inv_own[0], panel * PRW, col0, acc,
                                                            rs_ci, rs_cj, count);
                     if (HALVES == 2)
@@ -567,11 +567,11 @@ __global__ __launch_bounds__(512) void sim_i8p_kernel(SimI8PArgs a) {
         // with a ring of 2 the barrier at the top of the loop happened to outlast the single step in flight.)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    tail_close(a.tail_base, a.tail_shift, a.tail_fill, lane, &tail_sh[wave]);
+    tail_close(a.list, lane, &tail_sh[wave]);
 #if VSC_I8P_ABLATE
     if (ablate_sink == 0x7fffffff) count = -1;
 #endif
-    if (lane == 0) a.seg_count[seg] = count;
+    if (lane == 0) a.list.seg_count[seg] = count;
 }
 
 template <int NKC, int HALVES>
@@ -605,7 +605,7 @@ bool sim_i8p_pairs(int dpad8, int npanel, int nsteps, int slice, bool force) {
 int launch_sim_i8p(const SimI8PArgs& a, int grid, hipStream_t stream) {
     if (grid <= 0 || a.npanel <= 0 || a.nsteps <= 0) {
         // nothing to search: the caller's exact stage must see empty segments, not stale fill levels
-        if (grid > 0) VSC_HIP(hipMemsetAsync(a.seg_count, 0, (size_t)grid * 8 * sizeof(int), stream));
+        if (grid > 0) VSC_HIP(hipMemsetAsync(a.list.seg_count, 0, (size_t)a.list.n_seg * sizeof(int), stream));
         return VSC_OK;
     }
     VSC_HIP(hipMemsetAsync(a.next_slice, 0, ((size_t)a.npanel + 1) * sizeof(int), stream));

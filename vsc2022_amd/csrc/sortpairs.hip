@@ -48,35 +48,33 @@ static int bits_for(uint64_t maxval) {
 
 // Orders hits (device arrays, arbitrary order) by (score desc, i asc, j asc) and writes the first
 // min(n, K) to out_* (device).  `negate`: stored scores are negated distances (L2).
-int sort_hits_topk(const int32_t* hi, const int32_t* hj, const float* hs, int64_t n, int64_t K,
-                   int64_t max_i, int64_t max_j, DevBuf& w0, DevBuf& w1, DevBuf& w2, DevBuf& w3, DevBuf& tmp,
-                   int32_t* out_i, int32_t* out_j, float* out_s, int negate, int64_t* n_out,
-                   hipStream_t stream) {
+int sort_hits_topk(ConstHitView h, int64_t n, int64_t K, int64_t max_i, int64_t max_j, SortScratch& sc, HitView out,
+                   int negate, int64_t* n_out, hipStream_t stream) {
     const int64_t m = n < K ? n : K;
     *n_out = m;
     if (n <= 0) return VSC_OK;
-    VSC_TRY(w0.reserve(sizeof(uint64_t) * n));
-    VSC_TRY(w1.reserve(sizeof(uint64_t) * n));
-    VSC_TRY(w2.reserve(sizeof(uint32_t) * n));
-    VSC_TRY(w3.reserve(sizeof(uint32_t) * n));
-    uint64_t* k64a = w0.as<uint64_t>();
-    uint64_t* k64b = w1.as<uint64_t>();
-    uint32_t* k32a = w2.as<uint32_t>();
-    uint32_t* k32b = w3.as<uint32_t>();
-    hipLaunchKernelGGL(pack_hits_kernel, dim3(grid_for(n)), dim3(256), 0, stream, hi, hj, hs, n, k64a, k32a);
+    VSC_TRY(sc.w0.reserve(sizeof(uint64_t) * n));
+    VSC_TRY(sc.w1.reserve(sizeof(uint64_t) * n));
+    VSC_TRY(sc.w2.reserve(sizeof(uint32_t) * n));
+    VSC_TRY(sc.w3.reserve(sizeof(uint32_t) * n));
+    uint64_t* k64a = sc.w0.as<uint64_t>();
+    uint64_t* k64b = sc.w1.as<uint64_t>();
+    uint32_t* k32a = sc.w2.as<uint32_t>();
+    uint32_t* k32b = sc.w3.as<uint32_t>();
+    hipLaunchKernelGGL(pack_hits_kernel, dim3(grid_for(n)), dim3(256), 0, stream, h.i, h.j, h.s, n, k64a, k32a);
     VSC_HIP(hipGetLastError());
     const int end_bit = 32 + bits_for((uint64_t)(max_i > 0 ? max_i : 1));
-    VSC_TRY(tmp.reserve(radix_tmp_bytes(n)));
+    VSC_TRY(sc.tmp.reserve(radix_tmp_bytes(n)));
     // (row, ref) ascending, then -- stably -- score descending
     // (the reference rows occupy `max_j` bits of the low word: the passes over the zero bits above them are skipped)
     int w = radix_sort_pairs<uint64_t, uint32_t>(k64a, k64b, k32a, k32b, n, 0, max_j > 0 ? bits_for((uint64_t)max_j) : 32, false,
-                                                 tmp.p, stream, 32, end_bit);
+                                                 sc.tmp.p, stream, 32, end_bit);
     if (w < 0) { set_error("radix sort launch failed"); return VSC_ERR_HIP; }
     if (w) { std::swap(k64a, k64b); std::swap(k32a, k32b); }  // sorted pairs now in (k64a, k32a)
-    w = radix_sort_pairs<uint32_t, uint64_t>(k32a, k32b, k64a, k64b, n, 0, 32, true, tmp.p, stream);
+    w = radix_sort_pairs<uint32_t, uint64_t>(k32a, k32b, k64a, k64b, n, 0, 32, true, sc.tmp.p, stream);
     if (w < 0) { set_error("radix sort launch failed"); return VSC_ERR_HIP; }
     if (w) { std::swap(k64a, k64b); std::swap(k32a, k32b); }
-    hipLaunchKernelGGL(unpack_hits_kernel, dim3(grid_for(m)), dim3(256), 0, stream, k64a, k32a, m, out_i, out_j, out_s, negate);
+    hipLaunchKernelGGL(unpack_hits_kernel, dim3(grid_for(m)), dim3(256), 0, stream, k64a, k32a, m, out.i, out.j, out.s, negate);
     VSC_HIP(hipGetLastError());
     return VSC_OK;
 }
@@ -98,20 +96,19 @@ __global__ __launch_bounds__(256) void thr_keys_kernel(const float* __restrict__
     vals[x] = x;
 }
 
-int sort_rows_by_threshold(const float* thr, int64_t n, DevBuf& w0, DevBuf& w1, DevBuf& w2, DevBuf& w3, DevBuf& tmp,
-                           const int32_t** perm, hipStream_t stream) {
+int sort_rows_by_threshold(const float* thr, int64_t n, SortScratch& sc, const int32_t** perm, hipStream_t stream) {
     *perm = nullptr;
     if (n <= 0) return VSC_OK;
-    VSC_TRY(w0.reserve(sizeof(uint32_t) * n));
-    VSC_TRY(w1.reserve(sizeof(uint32_t) * n));
-    VSC_TRY(w2.reserve(sizeof(int32_t) * n));
-    VSC_TRY(w3.reserve(sizeof(int32_t) * n));
-    VSC_TRY(tmp.reserve(radix_tmp_bytes(n)));
-    uint32_t *ka = w0.as<uint32_t>(), *kb = w1.as<uint32_t>();
-    int32_t *va = w2.as<int32_t>(), *vb = w3.as<int32_t>();
+    VSC_TRY(sc.w0.reserve(sizeof(uint32_t) * n));
+    VSC_TRY(sc.w1.reserve(sizeof(uint32_t) * n));
+    VSC_TRY(sc.w2.reserve(sizeof(int32_t) * n));
+    VSC_TRY(sc.w3.reserve(sizeof(int32_t) * n));
+    VSC_TRY(sc.tmp.reserve(radix_tmp_bytes(n)));
+    uint32_t *ka = sc.w0.as<uint32_t>(), *kb = sc.w1.as<uint32_t>();
+    int32_t *va = sc.w2.as<int32_t>(), *vb = sc.w3.as<int32_t>();
     hipLaunchKernelGGL(thr_keys_kernel, dim3(grid_for(n)), dim3(256), 0, stream, thr, (int)n, ka, va);
     VSC_HIP(hipGetLastError());
-    const int w = radix_sort_pairs<uint32_t, int32_t>(ka, kb, va, vb, n, 0, 32, false, tmp.p, stream);
+    const int w = radix_sort_pairs<uint32_t, int32_t>(ka, kb, va, vb, n, 0, 32, false, sc.tmp.p, stream);
     if (w < 0) { set_error("radix sort launch failed"); return VSC_ERR_HIP; }
     *perm = w ? vb : va;
     return VSC_OK;
@@ -127,20 +124,19 @@ __global__ __launch_bounds__(256) void score_keys_kernel(const float* __restrict
     vals[x] = (int32_t)x;
 }
 
-int argsort_scores_desc(const float* s, int64_t n, DevBuf& w0, DevBuf& w1, DevBuf& w2, DevBuf& w3, DevBuf& tmp,
-                        const int32_t** perm, hipStream_t stream) {
+int argsort_scores_desc(const float* s, int64_t n, SortScratch& sc, const int32_t** perm, hipStream_t stream) {
     *perm = nullptr;
     if (n <= 0) return VSC_OK;
-    VSC_TRY(w0.reserve(sizeof(uint32_t) * n));
-    VSC_TRY(w1.reserve(sizeof(uint32_t) * n));
-    VSC_TRY(w2.reserve(sizeof(int32_t) * n));
-    VSC_TRY(w3.reserve(sizeof(int32_t) * n));
-    VSC_TRY(tmp.reserve(radix_tmp_bytes(n)));
-    uint32_t *ka = w0.as<uint32_t>(), *kb = w1.as<uint32_t>();
-    int32_t *va = w2.as<int32_t>(), *vb = w3.as<int32_t>();
+    VSC_TRY(sc.w0.reserve(sizeof(uint32_t) * n));
+    VSC_TRY(sc.w1.reserve(sizeof(uint32_t) * n));
+    VSC_TRY(sc.w2.reserve(sizeof(int32_t) * n));
+    VSC_TRY(sc.w3.reserve(sizeof(int32_t) * n));
+    VSC_TRY(sc.tmp.reserve(radix_tmp_bytes(n)));
+    uint32_t *ka = sc.w0.as<uint32_t>(), *kb = sc.w1.as<uint32_t>();
+    int32_t *va = sc.w2.as<int32_t>(), *vb = sc.w3.as<int32_t>();
     hipLaunchKernelGGL(score_keys_kernel, dim3(grid_for(n)), dim3(256), 0, stream, s, (long long)n, ka, va);
     VSC_HIP(hipGetLastError());
-    const int w = radix_sort_pairs<uint32_t, int32_t>(ka, kb, va, vb, n, 0, 32, true, tmp.p, stream);
+    const int w = radix_sort_pairs<uint32_t, int32_t>(ka, kb, va, vb, n, 0, 32, true, sc.tmp.p, stream);
     if (w < 0) { set_error("radix sort launch failed"); return VSC_ERR_HIP; }
     *perm = w ? vb : va;
     return VSC_OK;
@@ -189,13 +185,13 @@ __global__ __launch_bounds__(1024) void group_scale_rank_kernel(const int32_t* _
     out[base + rank] = row;
 }
 
-int sort_rows_by_threshold_then_scale(const float* thr, const float* scale, int64_t n, int group_shift, DevBuf& w0, DevBuf& w1,
-                                      DevBuf& w2, DevBuf& w3, DevBuf& tmp, const int32_t** perm, hipStream_t stream) {
-    VSC_TRY(sort_rows_by_threshold(thr, n, w0, w1, w2, w3, tmp, perm, stream));
+int sort_rows_by_threshold_then_scale(const float* thr, const float* scale, int64_t n, int group_shift, SortScratch& sc,
+                                      const int32_t** perm, hipStream_t stream) {
+    VSC_TRY(sort_rows_by_threshold(thr, n, sc, perm, stream));
     if (n <= 0 || (n >> group_shift) >= 4096) return VSC_OK;  // (12 bits of group number)
     if (group_shift <= 10) {
         int32_t* va = const_cast<int32_t*>(*perm);
-        int32_t* vb = va == w2.as<int32_t>() ? w3.as<int32_t>() : w2.as<int32_t>();
+        int32_t* vb = va == sc.w2.as<int32_t>() ? sc.w3.as<int32_t>() : sc.w2.as<int32_t>();
         const int G = 1 << group_shift;
         hipLaunchKernelGGL(group_scale_rank_kernel, dim3((unsigned)((n + G - 1) >> group_shift)), dim3(std::max(64, G)), 0, stream,
                            va, scale, (int)n, group_shift, vb);
@@ -203,12 +199,12 @@ int sort_rows_by_threshold_then_scale(const float* thr, const float* scale, int6
         *perm = vb;
         return VSC_OK;
     }
-    uint32_t *ka = w0.as<uint32_t>(), *kb = w1.as<uint32_t>();
+    uint32_t *ka = sc.w0.as<uint32_t>(), *kb = sc.w1.as<uint32_t>();
     int32_t* va = const_cast<int32_t*>(*perm);
-    int32_t* vb = va == w2.as<int32_t>() ? w3.as<int32_t>() : w2.as<int32_t>();
+    int32_t* vb = va == sc.w2.as<int32_t>() ? sc.w3.as<int32_t>() : sc.w2.as<int32_t>();
     hipLaunchKernelGGL(group_scale_keys_kernel, dim3(grid_for(n)), dim3(256), 0, stream, va, scale, (int)n, group_shift, ka);
     VSC_HIP(hipGetLastError());
-    const int w = radix_sort_pairs<uint32_t, int32_t>(ka, kb, va, vb, n, 0, 32, false, tmp.p, stream);
+    const int w = radix_sort_pairs<uint32_t, int32_t>(ka, kb, va, vb, n, 0, 32, false, sc.tmp.p, stream);
     if (w < 0) { set_error("radix sort launch failed"); return VSC_ERR_HIP; }
     *perm = w ? vb : va;
     return VSC_OK;
@@ -289,28 +285,27 @@ __global__ __launch_bounds__(256) void pair_out_kernel(const uint32_t* head_rank
 // All pointers device.  hits are in search order (score-descending).  Synchronises the stream once
 // (the pair count sizes the second sort).
 int pair_max_device(const int32_t* hi, const int32_t* hj, const float* hs, int64_t n,
-                    const int32_t* row2q, const int32_t* row2r, int64_t nq_rows, int64_t nr_rows, DevBuf& w0,
-                    DevBuf& w1, DevBuf& w2, DevBuf& w3, DevBuf& tmp, DevBuf& cnt, int32_t* out_q,
-                    int32_t* out_r, float* out_s, int64_t* out_first, int64_t cap, int64_t* n_pairs,
-                    hipStream_t stream) {
+                    const int32_t* row2q, const int32_t* row2r, int64_t nq_rows, int64_t nr_rows, SortScratch& sc,
+                    DevBuf& cnt, int32_t* out_q, int32_t* out_r, float* out_s, int64_t* out_first, int64_t cap,
+                    int64_t* n_pairs, hipStream_t stream) {
     *n_pairs = 0;
     if (n <= 0) return VSC_OK;
     if (n > 0xffffffffLL) {
         set_error("pair_max: more than 2^32 hits");
         return VSC_ERR_INVALID;
     }
-    VSC_TRY(w0.reserve(sizeof(uint64_t) * n));
-    VSC_TRY(w1.reserve(sizeof(uint64_t) * n));
-    VSC_TRY(w2.reserve(sizeof(uint32_t) * n));
-    VSC_TRY(w3.reserve(sizeof(uint32_t) * n));
+    VSC_TRY(sc.w0.reserve(sizeof(uint64_t) * n));
+    VSC_TRY(sc.w1.reserve(sizeof(uint64_t) * n));
+    VSC_TRY(sc.w2.reserve(sizeof(uint32_t) * n));
+    VSC_TRY(sc.w3.reserve(sizeof(uint32_t) * n));
     VSC_TRY(cnt.reserve(sizeof(unsigned long long)));
-    uint64_t* ka = w0.as<uint64_t>();
-    uint64_t* kb = w1.as<uint64_t>();
-    uint32_t* ra = w2.as<uint32_t>();
-    uint32_t* rb = w3.as<uint32_t>();
+    uint64_t* ka = sc.w0.as<uint64_t>();
+    uint64_t* kb = sc.w1.as<uint64_t>();
+    uint32_t* ra = sc.w2.as<uint32_t>();
+    uint32_t* rb = sc.w3.as<uint32_t>();
     hipLaunchKernelGGL(pair_key_kernel, dim3(grid_for(n)), dim3(256), 0, stream, hi, hj, n, row2q, row2r, ka, ra);
     VSC_HIP(hipGetLastError());
-    VSC_TRY(tmp.reserve(radix_tmp_bytes(n)));
+    VSC_TRY(sc.tmp.reserve(radix_tmp_bytes(n)));
     // the key is (query video << 32 | ref video): only the bits the largest ordinals occupy are sorted (40 000 videos a
     // side: 2 + 2 passes instead of 8)
     VSC_TRY(cnt.reserve(sizeof(unsigned long long)));
@@ -323,7 +318,7 @@ int pair_max_device(const int32_t* hi, const int32_t* hj, const float* hs, int64
     VSC_HIP(hipMemcpyAsync(mxh, mx, sizeof(mxh), hipMemcpyDeviceToHost, stream));
     VSC_HIP(hipStreamSynchronize(stream));
     const int bits_q = bits_for((uint64_t)std::max(mxh[0], 1u)), bits_r = bits_for((uint64_t)std::max(mxh[1], 1u));
-    int w = radix_sort_pairs<uint64_t, uint32_t>(ka, kb, ra, rb, n, 0, bits_r, false, tmp.p, stream, 32, 32 + bits_q);
+    int w = radix_sort_pairs<uint64_t, uint32_t>(ka, kb, ra, rb, n, 0, bits_r, false, sc.tmp.p, stream, 32, 32 + bits_q);
     if (w < 0) { set_error("radix sort launch failed"); return VSC_ERR_HIP; }
     if (!w) { std::swap(ka, kb); std::swap(ra, rb); }  // sorted pairs in (kb, rb); (ka, ra) are free
     VSC_HIP(hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long), stream));
@@ -340,7 +335,7 @@ int pair_max_device(const int32_t* hi, const int32_t* hj, const float* hs, int64
         return VSC_ERR_CAPACITY;
     }
     // first-appearance order = ascending rank of the heads (4 passes: the result is back in (ra, ka))
-    w = radix_sort_pairs<uint32_t, uint64_t>(ra, rb, ka, kb, (int64_t)np, 0, 32, false, tmp.p, stream);
+    w = radix_sort_pairs<uint32_t, uint64_t>(ra, rb, ka, kb, (int64_t)np, 0, 32, false, sc.tmp.p, stream);
     if (w < 0) { set_error("radix sort launch failed"); return VSC_ERR_HIP; }
     if (w) { std::swap(ka, kb); std::swap(ra, rb); }
     hipLaunchKernelGGL(pair_out_kernel, dim3(grid_for((int64_t)np)), dim3(256), 0, stream, ra, ka, hs,
@@ -382,31 +377,30 @@ __global__ __launch_bounds__(256) void knn_cut_kernel(const uint64_t* key64, con
     out_j[x] = have ? (int64_t)ref[e] : -1;
 }
 
-int knn_from_hits(const int32_t* hi, const int32_t* hj, const float* hs, int64_t n, int64_t nq, int k, DevBuf& w0,
-                  DevBuf& w1, DevBuf& w2, DevBuf& w3, DevBuf& tmp, float* out_s, int64_t* out_j,
+int knn_from_hits(ConstHitView h, int64_t n, int64_t nq, int k, SortScratch& sc, float* out_s, int64_t* out_j,
                   hipStream_t stream) {
     const int64_t nn = n > 0 ? n : 1;
-    VSC_TRY(w0.reserve(sizeof(uint64_t) * nn));
-    VSC_TRY(w1.reserve(sizeof(uint64_t) * nn));
-    VSC_TRY(w2.reserve(sizeof(uint32_t) * nn));
-    VSC_TRY(w3.reserve(sizeof(uint32_t) * nn));
-    uint64_t* ka = w0.as<uint64_t>();
-    uint64_t* kb = w1.as<uint64_t>();
-    uint32_t* ra = w2.as<uint32_t>();
-    uint32_t* rb = w3.as<uint32_t>();
+    VSC_TRY(sc.w0.reserve(sizeof(uint64_t) * nn));
+    VSC_TRY(sc.w1.reserve(sizeof(uint64_t) * nn));
+    VSC_TRY(sc.w2.reserve(sizeof(uint32_t) * nn));
+    VSC_TRY(sc.w3.reserve(sizeof(uint32_t) * nn));
+    uint64_t* ka = sc.w0.as<uint64_t>();
+    uint64_t* kb = sc.w1.as<uint64_t>();
+    uint32_t* ra = sc.w2.as<uint32_t>();
+    uint32_t* rb = sc.w3.as<uint32_t>();
     if (n > 0) {
-        hipLaunchKernelGGL(knn_keys_kernel, dim3(grid_for(n)), dim3(256), 0, stream, hi, hs, n, ka);
+        hipLaunchKernelGGL(knn_keys_kernel, dim3(grid_for(n)), dim3(256), 0, stream, h.i, h.s, n, ka);
         VSC_HIP(hipGetLastError());
         // the sort ping-pongs between its buffers: work on a copy of the refs, the hit list stays intact
-        VSC_HIP(hipMemcpyAsync(ra, hj, (size_t)n * 4, hipMemcpyDeviceToDevice, stream));
+        VSC_HIP(hipMemcpyAsync(ra, h.j, (size_t)n * 4, hipMemcpyDeviceToDevice, stream));
         const int end_bit = 32 + bits_for((uint64_t)(nq > 0 ? nq : 1));
-        VSC_TRY(tmp.reserve(radix_tmp_bytes(n)));
+        VSC_TRY(sc.tmp.reserve(radix_tmp_bytes(n)));
         // 1. refs ascending (payload: the row/score key) ...
-        int w = radix_sort_pairs<uint32_t, uint64_t>(ra, rb, ka, kb, n, 0, 32, false, tmp.p, stream);
+        int w = radix_sort_pairs<uint32_t, uint64_t>(ra, rb, ka, kb, n, 0, 32, false, sc.tmp.p, stream);
         if (w < 0) { set_error("radix sort launch failed"); return VSC_ERR_HIP; }
         if (w) { std::swap(ka, kb); std::swap(ra, rb); }
         // 2. ... then, stably, row ascending / score descending
-        w = radix_sort_pairs<uint64_t, uint32_t>(ka, kb, ra, rb, n, 0, end_bit, false, tmp.p, stream);
+        w = radix_sort_pairs<uint64_t, uint32_t>(ka, kb, ra, rb, n, 0, end_bit, false, sc.tmp.p, stream);
         if (w < 0) { set_error("radix sort launch failed"); return VSC_ERR_HIP; }
         if (w) { std::swap(ka, kb); std::swap(ra, rb); }
     }
@@ -436,11 +430,11 @@ __global__ __launch_bounds__(256) void knn_seed_hits_kernel(const float* __restr
     }
 }
 
-int launch_knn_seed_hits(const float* knn_s, const int64_t* knn_j, int64_t nq, int k, int32_t* hi, int32_t* hj, float* hs,
-                         unsigned long long* counter, hipStream_t stream) {
+int launch_knn_seed_hits(const float* knn_s, const int64_t* knn_j, int64_t nq, int k, HitView h, unsigned long long* counter,
+                         hipStream_t stream) {
     const int64_t n = nq * k;
     if (n <= 0) return VSC_OK;
-    hipLaunchKernelGGL(knn_seed_hits_kernel, dim3(grid_for(n)), dim3(256), 0, stream, knn_s, knn_j, n, k, hi, hj, hs, counter);
+    hipLaunchKernelGGL(knn_seed_hits_kernel, dim3(grid_for(n)), dim3(256), 0, stream, knn_s, knn_j, n, k, h.i, h.j, h.s, counter);
     VSC_HIP(hipGetLastError());
     return VSC_OK;
 }
@@ -461,25 +455,23 @@ int launch_knn_row_thr(const float* knn_s, int64_t nq, int k, float* row_thr, in
 }
 
 // faiss range_search order: rows ascending, refs ascending within a row (device in/out).
-int sort_hits_rowcol(const int32_t* hi, const int32_t* hj, const float* hs, int64_t n, DevBuf& w0,
-                     DevBuf& w1, DevBuf& w2, DevBuf& w3, DevBuf& tmp, int32_t* out_i, int32_t* out_j,
-                     float* out_s, int negate, hipStream_t stream) {
+int sort_hits_rowcol(ConstHitView h, int64_t n, SortScratch& sc, HitView out, int negate, hipStream_t stream) {
     if (n <= 0) return VSC_OK;
-    VSC_TRY(w0.reserve(sizeof(uint64_t) * n));
-    VSC_TRY(w1.reserve(sizeof(uint64_t) * n));
-    VSC_TRY(w2.reserve(sizeof(uint32_t) * n));
-    VSC_TRY(w3.reserve(sizeof(uint32_t) * n));
-    uint64_t* k64a = w0.as<uint64_t>();
-    uint64_t* k64b = w1.as<uint64_t>();
-    uint32_t* k32a = w2.as<uint32_t>();
-    uint32_t* k32b = w3.as<uint32_t>();
-    hipLaunchKernelGGL(pack_hits_kernel, dim3(grid_for(n)), dim3(256), 0, stream, hi, hj, hs, n, k64a, k32a);
+    VSC_TRY(sc.w0.reserve(sizeof(uint64_t) * n));
+    VSC_TRY(sc.w1.reserve(sizeof(uint64_t) * n));
+    VSC_TRY(sc.w2.reserve(sizeof(uint32_t) * n));
+    VSC_TRY(sc.w3.reserve(sizeof(uint32_t) * n));
+    uint64_t* k64a = sc.w0.as<uint64_t>();
+    uint64_t* k64b = sc.w1.as<uint64_t>();
+    uint32_t* k32a = sc.w2.as<uint32_t>();
+    uint32_t* k32b = sc.w3.as<uint32_t>();
+    hipLaunchKernelGGL(pack_hits_kernel, dim3(grid_for(n)), dim3(256), 0, stream, h.i, h.j, h.s, n, k64a, k32a);
     VSC_HIP(hipGetLastError());
-    VSC_TRY(tmp.reserve(radix_tmp_bytes(n)));
-    const int w = radix_sort_pairs<uint64_t, uint32_t>(k64a, k64b, k32a, k32b, n, 0, 64, false, tmp.p, stream);
+    VSC_TRY(sc.tmp.reserve(radix_tmp_bytes(n)));
+    const int w = radix_sort_pairs<uint64_t, uint32_t>(k64a, k64b, k32a, k32b, n, 0, 64, false, sc.tmp.p, stream);
     if (w < 0) { set_error("radix sort launch failed"); return VSC_ERR_HIP; }
     if (w) { std::swap(k64a, k64b); std::swap(k32a, k32b); }
-    hipLaunchKernelGGL(unpack_hits_kernel, dim3(grid_for(n)), dim3(256), 0, stream, k64a, k32a, n, out_i, out_j, out_s, negate);
+    hipLaunchKernelGGL(unpack_hits_kernel, dim3(grid_for(n)), dim3(256), 0, stream, k64a, k32a, n, out.i, out.j, out.s, negate);
     VSC_HIP(hipGetLastError());
     return VSC_OK;
 }
