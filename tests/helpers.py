@@ -159,3 +159,51 @@ def check_localisation_sample(orc, q_feats, q_off, r_feats, r_off, pair_q, pair_
             assert score.view(np.uint32) == np.float32(bscore[k, b_]).view(np.uint32), (int(k), b_, float(score), float(bscore[k, b_]))
         n_boxes += len(exp)
     return len(pick), n_boxes
+
+
+# ---- a candidate list whose segments are too small for one dense wave tile (test_gpu_prefilter.py, test_gpu_i8.py)
+
+def full_segment_case(d=64):
+    """300 query rows x 2000 references with ONE dense wave tile: query rows 0-127 and references 0-63 are copies of one
+    unit row (128 x 64 = 8192 pairs of score ~1), everything else random unit rows (scores ~N(0, 1/d): 7 sigma below the
+    radius 0.9).  In the 128 x 64 wave tile of the fp16 kernels those 8192 pairs belong to one wave; the int8 launch
+    sorts its rows first and may split them over two to four waves (test_gpu_i8.py)."""
+    rng = np.random.default_rng(77)
+    q, r = (x / np.linalg.norm(x, axis=1, keepdims=True)
+            for x in (rng.standard_normal((n, d)).astype(np.float32) for n in (300, 2000)))
+    q[:128] = q[0]
+    r[:64] = q[0]
+    return q, r, 0.9, 8192
+
+
+def full_segment_capacity(nq, nr, ring, tile_cands, n_hits):
+    """A hit capacity with which the dense wave tile of full_segment_case overflows its wave's private segment of the
+    candidate list and goes on in the shared tail (cand_list.h: cand_reserve -> tail_take), while nothing overflows.
+
+    A range search plans one candidate list of ccap = cap entries per launch (api_search.hip: cand_list_plan):
+        n_seg = 8 * grid, seg_cap = cap // n_seg, tail_cap = (4 * cap + 2048 * 128) - seg_cap * n_seg
+    with grid = sim_f16_grid: min(256, 8 * ceil(tq * tr / 8)), tq = ceil(nq / 256), tr = ceil(nr / 256) for the ring kernel,
+    and sim_f16p_plan's for the panel kernels (fp16 and int8): P = ceil(nq / 128) panels, S = ceil(nr / 512) col-steps,
+    slice = min(max(4, min(64, S * P // 4096)), max(S, 1)), grid = max(1, min(256, P * ceil(S / slice))).
+    300 x 2000: ring grid 16 -> 128 segments; panel grid 3 -> 24 segments.  cap = 16384: seg_cap = 128 / 682."""
+    cap = 16384
+    if ring:
+        tq, tr = -(-nq // 256), -(-nr // 256)
+        grid = min(256, 8 * -(-(tq * tr) // 8))
+    else:
+        P, S = -(-nq // 128), -(-nr // 512)
+        sl = min(max(4, min(64, S * P // 4096)), max(S, 1))
+        grid = max(1, min(256, P * -(-S // sl)))
+    n_seg = 8 * grid
+    seg_cap = cap // n_seg
+    tail_cap = 4 * cap + 2048 * 128 - seg_cap * n_seg
+    assert seg_cap < tile_cands, "the dense wave tile no longer fills its wave's segment: the tail is not reached"
+    # (seg_cap < 8192 also keeps the launch off the fast emitters, which want room for a whole tile in the segment)
+    assert n_hits <= cap, "the kept-hit list would overflow"
+    # the tail is handed out in chunks (cand_list.h: tail_chunk_shift_for); the dense pairs sit in at most two waves,
+    # each of which leaves at most one chunk partly filled
+    shift = 6
+    while shift < 12 and (2 << shift) <= tail_cap // (8 * n_seg):
+        shift += 1
+    assert tail_cap >= 3 * cap and tail_cap >= n_hits + 2 * (1 << shift), "the candidates would not fit the tail"
+    return cap

@@ -516,3 +516,32 @@ def test_knn_rows_per_launch_do_not_change_results(gpu, k):
     assert outs[0][2]["i8_launches"] < outs[1][2]["i8_launches"]      # fewer, larger launches
     for o in outs[1:]:
         assert np.array_equal(outs[0][1], o[1]) and np.array_equal(bits(outs[0][0]), bits(o[0]))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pair", [0, 2])
+def test_int8_full_segment_continues_in_the_shared_tail(gpu, orc, pair):
+    """The int8 kernel's general emitter with a full private segment: the wave goes on in the shared tail (cand_list.h:
+    cand_reserve).  Shape and capacity are tests/helpers.py's (full_segment_case / full_segment_capacity: the int8
+    launch uses the panel kernels' plan).  The int8 launch sees its rows sorted by their largest element: the 128
+    identical query rows stay neighbours but may straddle two work items, so one wave tile holds at least 64 of them
+    x its 64 (unpaired) or 32 (paired: 256 x 32 tiles) of the identical references = 4096 / 2048 candidates -- both far
+    above seg_cap = 682."""
+    from helpers import full_segment_capacity, full_segment_case
+    from vsc2022_amd.vsc.index import FlatIndex
+
+    q, r, radius, tile_cands = full_segment_case()
+    olims, oD, oI = orc.range_search(q, r, radius)
+    assert len(oI) == tile_cands
+    idx = FlatIndex(q.shape[1], options=opts(VSC_PREFILTER="2", VSC_I8="2", VSC_I8P_PAIR=str(pair)))
+    idx.profile(True)
+    idx.set_hit_capacity(full_segment_capacity(len(q), len(r), False, tile_cands // 4 if pair else tile_cands // 2, len(oI)))
+    idx.add(r)
+    lims, D, I = idx.range_search(q, radius)
+    assert np.array_equal(lims, olims) and np.array_equal(I, oI)
+    assert np.array_equal(bits(D), bits(oD))
+    assert i8_launches(idx) > 0                             # the int8 kernel really ran ...
+    assert idx.get_option("i8p_pair") == pair
+    # (i8p_pair = 2 pairs every launch the shape can take -- sim_i8p_pairs: int8 rows of at most 512 bytes, one panel)
+    assert q.shape[1] <= 512 and len(q) >= 1
+    assert idx.get_option("i8_fallbacks") == 0              # ... and the search never left it for fp16

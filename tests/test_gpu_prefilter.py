@@ -1,4 +1,4 @@
-"""fp16 pre-filter + exact re-scoring (csrc/sim_f16.hip) must be INVISIBLE in the results.
+"""fp16 pre-filter + exact re-scoring (csrc/sim_f16*.hip, rescore.hip) must be INVISIBLE in the results.
 
 The thresholded searches evaluate the bulk of the score matrix in fp16 and hand to the exact fp32
 stage every pair whose fp16 score plus a rigorous error bound exceeds the radius.  The candidate set is
@@ -281,3 +281,24 @@ def test_fast_emission_path_matches_oracle(gpu, orc, seed, nq, nr, d, K):
     assert_same((i, j, s), (oi, oj, os_))
     assert np.float32(radius) == np.float32(info["radius"])
     assert search_stats(idx) >= len(os_)
+
+
+@pytest.mark.parametrize("kernel", ["panel", "ring"])
+def test_full_segment_continues_in_the_shared_tail(gpu, orc, kernel):
+    """A wave whose private segment is full goes on in its chunk of the shared tail (cand_list.h: cand_reserve): pinned
+    for the panel kernel and the LDS-ring kernel with a capacity derived from the launch plan (tests/helpers.py: full_segment_capacity)."""
+    from helpers import full_segment_capacity, full_segment_case
+    from vsc2022_amd.vsc.index import FlatIndex
+
+    q, r, radius, tile_cands = full_segment_case()
+    olims, oD, oI = orc.range_search(q, r, radius)
+    assert len(oI) == tile_cands                            # the dense tile, nothing else
+    ring = kernel == "ring"
+    # (i8=0: the fp16 kernels also where a parity suite runs this file with the int8 kernel switched on)
+    idx = FlatIndex(q.shape[1], options=prefilter_options("2", f16_kernel=1 if ring else 0, i8=0))
+    assert idx.get_option("f16_kernel") == (1 if ring else 0)
+    idx.set_hit_capacity(full_segment_capacity(len(q), len(r), ring, tile_cands, len(oI)))
+    idx.add(r)
+    lims, D, I = idx.range_search(q, radius)                # (an overflow of either list is an error here, not a rerun)
+    assert np.array_equal(lims, olims) and np.array_equal(I, oI)
+    assert np.array_equal(bits(D), bits(oD))

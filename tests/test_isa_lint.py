@@ -86,7 +86,7 @@ def test_lint_on_hand_assembled_snippets(tmp_path, name):
 
 
 def test_shipped_library_is_clean():
-    """every kernel of vsc2022_amd/libvscmi.so (all 13 code objects): no VALU-SGPR -> VMEM / lane-select / m0 hazard,
+    """every kernel of vsc2022_amd/libvscmi.so (all 14 code objects): no VALU-SGPR -> VMEM / lane-select / m0 hazard,
     and no touch of a register that an outstanding load still owns"""
     import lint_isa
 

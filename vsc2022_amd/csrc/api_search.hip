@@ -231,14 +231,14 @@ static int exact_stage(vsc_index* idx, const F16Batch& b, int64_t cap, const Can
     r.cap = cap;
     r.row_thr = b.row_thr;
     r.j0 = (int)b.nr_begin;
-    if (sq16(idx)) {  // the reference rows come from the fp16 store (sim_f16.hip: rescore_list<SRC>)
+    if (sq16(idx)) {  // the reference rows come from the fp16 store (rescore.hip: rescore_list<SRC>)
         r.R = nullptr;
         r.Rh = idx->refh.as<_Float16>();
         r.dpadh = idx->dpadh;
         r.rsrc = idx->frag ? 2 : 1;
     }
     // The candidates are compacted out of the waves' segments, sorted by reference row and re-scored as one dense
-    // list (sim_f16.hip, "candidates ordered by reference row"): 74 -> 54 ms per bench step, k-NN k = 20 140 ->
+    // list (rescore.hip, "candidates ordered by reference row"): 74 -> 54 ms per bench step, k-NN k = 20 140 ->
     // 100 ms.  It needs the candidate count on the host (buffer sizes, grid of the sort): one stream sync per
     // launch, ~20 us against launches of 3-30 ms.  VSC_RESCORE_SORT=0: the segments as they are.
     if (!idx->rescore_by_ref) return launch_rescore(r, idx->stream);
@@ -260,7 +260,7 @@ static int exact_stage(vsc_index* idx, const F16Batch& b, int64_t cap, const Can
     VSC_TRY(launch_cand_compact(r, n_chunks_max, cs[0], cs[2], csn, idx->stream));
     const uint32_t *sj = nullptr, *si = nullptr;
     VSC_TRY(sort_candidates_by_ref(cs[0], cs[1], cs[2], cs[3], (int64_t)n_c, b.nr_end, ws.cstmp, &sj, &si, idx->stream));
-    // VSC_I8_SCREEN=1: int8 launches pass an fp16 screen first (sim_f16.hip: f16_screen_kernel).  Measured
+    // VSC_I8_SCREEN=1: int8 launches pass an fp16 screen first (rescore.hip: f16_screen_kernel).  Measured
     // neutral and therefore OFF by default: 29 % of the int8 candidates survive it (bench, 128 M -> 37 M per
     // step), the screen moves half the bytes per pair (23.8 ms) and the exact stage then costs 35.6 instead of
     // 59.8 ms -- both stages gather one query row per pair from the Infinity Cache at ~6 TB/s, which is the

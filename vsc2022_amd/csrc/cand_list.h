@@ -3,7 +3,7 @@
 // ballot group: with skewed candidate distributions (score-normalised descriptors: a few percent of the query rows
 // own most of the hits) a third of a launch's candidates can take this route, and 2048 waves queueing on one
 // counter once per handful of candidates turned 40 ms launches into seconds.  A wave keeps its current chunk as a
-// private extension of its segment; what it leaves unused is marked i = -1, which rescore_list skips.
+// private extension of its segment; every chunk has a fill level (tail_fill), and rescore_list skips what lies past it.
 #pragma once
 #include "vscmi_common.h"
 
@@ -48,11 +48,7 @@ __device__ __forceinline__ bool tail_take(const CandList& l, int total, int ln, 
     int left = e->left;
     long long p = e->pos;
     if (left < 0) return false;
-    if (total > chunk) {  // (only the block-at-a-time emitter asks for more than 64 at once: rerun with larger buffers)
-        if (ln == 0) { atomicOr(l.overflow, 2); e->left = -1; }
-        return false;
-    }
-    if (total > left) {
+    if (total > left) {  // (total <= 64 <= chunk: a fresh chunk always has the room)
         // close the current chunk (its fill level), take the next one
         if (ln == 0 && e->have) l.tail_fill[(p - 1 - (long long)l.tail_base) >> l.tail_shift] = chunk - left;
         unsigned long long base = 0;
@@ -68,6 +64,20 @@ __device__ __forceinline__ bool tail_take(const CandList& l, int total, int ln, 
     pos = p;
     if (ln == 0) { e->pos = p + total; e->left = left - total; e->have = 1; }
     return true;
+}
+
+// Room for the `total` (<= 64) candidates of one ballot group: in the wave's private segment (entries [seg_base,
+// seg_base + seg_cap), `count` = its wave-uniform fill level) while they fit -- candidates are not spread evenly --
+// else in the wave's chunk of the shared tail.  true and `pos` = first entry, or false (tail_take).  The general
+// emitters of the three pre-filter kernels call it; like tail_take it is inlined into their unrolled loops: no loop.
+__device__ __forceinline__ bool cand_reserve(const CandList& l, int64_t seg_base, int& count, int total, int ln,
+                                             TailExt* e, int64_t& pos) {
+    if (count + total <= l.seg_cap) {
+        pos = seg_base + count;
+        count += total;
+        return true;
+    }
+    return tail_take(l, total, ln, e, pos);
 }
 
 // at the end of the kernel: the fill level of the wave's last chunk

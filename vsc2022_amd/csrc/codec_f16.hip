@@ -6,7 +6,7 @@
 //   unpack_rows       packed fp32 rows -> row-major fp32 (vsc_index_reconstruct of a Flat handle)
 //   half_to_float     row-major fp16 -> row-major fp32 (vsc_index_add_f16 on a Flat handle)
 //   score_matrix_h16  the explicit score matrix (L2, k > 64) with the reference side read from the store
-// The exact stage's own fp16-source form is in sim_f16.hip (rescore_list<SRC>).
+// The exact stage's own fp16-source form is in rescore.hip (rescore_list<SRC>).
 #include "kernels.h"
 
 namespace vscmi {
@@ -16,7 +16,7 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 // index of the 16-byte piece holding k = 8 p .. 8 p + 7 of row j
 template <bool FRAG>
 __device__ __forceinline__ int64_t store_piece(int64_t j, int p, int dpadh) {
-    if (FRAG) return ((j >> 6) * (dpadh / 16) + (p >> 1)) * 128 + ((j >> 5) & 1) * 64 + (p & 1) * 32 + (j & 31);
+    if (FRAG) return frag_piece(j, p, dpadh);
     return j * (dpadh / 8) + p;
 }
 

@@ -25,7 +25,7 @@ struct SimThreshArgs {
     unsigned long long* counter; long long cap; int* overflow;
 };
 // fp16 pre-filter (sim_f16.hip): emits every (row, ref) whose fp16 score PLUS the tile's error bound
-// exceeds *radius -- a superset of the exact hits; rescore_candidates then applies the exact test.
+// exceeds *radius -- a superset of the exact hits; the exact stage (rescore.hip) then applies the exact test.
 struct SimF16Args {
     const _Float16* Q; const _Float16* R;  // fp16 images [rows pad 256][dpadh], natural k order
     const float* qn; const float* rn;      // per-row upper bounds of the L2 norm (+inf: row not representable)
@@ -42,6 +42,16 @@ struct SimF16Args {
 constexpr int F16P_PANEL_ROWS = 128;  // query rows per LDS-resident panel
 constexpr int F16P_COL_STEP = 512;    // reference columns per workgroup step (8 waves x 64); row padding of the image
 constexpr int F16P_MAX_DPADH = 512;   // the panel must fit the LDS: 128 rows x dpadh x 2 B <= 128 KiB
+// The fragment-major fp16 image: index of the 16-byte piece `piece` (k = 8 piece .. 8 piece + 7) of row `row`.  Rows
+// are grouped in wave tiles of 64 (two 32-row MFMA blocks); per k-step of 16 a tile holds 128 pieces: block, k half,
+// row inside the block -- the B operand of one v_mfma_f32_32x32x16_f16 (lane l: row l & 31, k half l >> 5) is 1 KiB
+// of consecutive memory.  The writers (layout.hip, codec_f16.hip) and the codec's readers go through here; the panel
+// kernel reads whole fragments by construction, and the exact stage (rescore.hip: rescore_list, f16_screen_kernel)
+// spells the same index out.  (Row: the caller's own integer type -- only the tile index needs 64 bits)
+template <typename Row>
+__host__ __device__ __forceinline__ int64_t frag_piece(Row row, int piece, int dpadh) {
+    return (int64_t)(row >> 6) * (dpadh / 16) * 128 + ((row >> 5) & 1) * 64 + (row & 31) + (piece >> 1) * 128 + (piece & 1) * 32;
+}
 struct SimF16PArgs {
     const _Float16* Q; const void* Rf;
     const float* qn; const float* rn;      // per-row upper bounds of the L2 norm (+inf: row not representable)
@@ -98,7 +108,7 @@ struct RescoreArgs {
     // natural layout; 2 = Rh fragment-major) and converted in registers; the chain is the same
     const _Float16* Rh = nullptr; int dpadh = 0; int rsrc = 0;
 };
-// fp16 screen of the int8 route's candidates (sim_f16.hip): the pair list sorted by reference row in, the pairs whose
+// fp16 screen of the int8 route's candidates (rescore.hip): the pair list sorted by reference row in, the pairs whose
 // fp16 score + error bound still reaches the threshold out
 struct ScreenArgs {
     const _Float16* Qh; const float* qn;  // row-major fp16 query image, norm bounds (absolute rows)

@@ -82,11 +82,10 @@ int launch_pack_half(const float* src, int64_t n, int dim, _Float16* dst, float*
 
 // The same for the REFERENCE side of the panel-stationary pre-filter (sim_f16p.hip): fragment-major image.
 // Rows are grouped in wave tiles of 64 (two 32-row MFMA blocks n = 0, 1); the 16-byte piece holding k =
-// 16 ks + 8 h .. + 7 of row j sits at piece index
-//     ((j / 64) * (dpadh / 16) + ks) * 128 + ((j / 32) & 1) * 64 + h * 32 + (j % 32)
-// i.e. the B operand of one v_mfma_f32_32x32x16_f16 (lane l: row l & 31, k half l >> 5) is 1 KiB of
-// consecutive memory.  `row0` = absolute index of the first row written (incremental adds append to a
-// partly filled tile); rows [row0 + n, row0 + rows_out) are zero filled.  One wave per row, one piece per lane.
+// 8 c .. + 7 of row j sits at piece index frag_piece(j, c, dpadh) (kernels.h), i.e. the B operand of one
+// v_mfma_f32_32x32x16_f16 (lane l: row l & 31, k half l >> 5) is 1 KiB of consecutive memory.  `row0` =
+// absolute index of the first row written (incremental adds append to a partly filled tile); rows
+// [row0 + n, row0 + rows_out) are zero filled.  One wave per row, one piece per lane.
 __global__ __launch_bounds__(256) void pack_half_frag_kernel(const float* __restrict__ src, int64_t n, int dim,
                                                              _Float16* __restrict__ image, float* __restrict__ norms,
                                                              int64_t row0, int64_t rows_out, int dpadh) {
@@ -95,7 +94,6 @@ __global__ __launch_bounds__(256) void pack_half_frag_kernel(const float* __rest
     const int64_t rel = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (rel >= rows_out) return;
     const int64_t row = row0 + rel;
-    const int nks = dpadh / 16;
     const float* r = src + rel * dim;
     float ss = 0.0f;
     bool bad = false;
@@ -109,9 +107,7 @@ __global__ __launch_bounds__(256) void pack_half_frag_kernel(const float* __rest
             ss = __fmaf_rn(x, x, ss);
             h[e] = (_Float16)x;  // round to nearest even
         }
-        const int ks = c >> 1, hh = c & 1;
-        const int64_t piece = ((row >> 6) * nks + ks) * 128 + ((row >> 5) & 1) * 64 + hh * 32 + (row & 31);
-        reinterpret_cast<f16x8*>(image)[piece] = h;
+        reinterpret_cast<f16x8*>(image)[frag_piece(row, c, dpadh)] = h;
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off);

@@ -20,13 +20,9 @@
 // twice, a third less LDS read traffic, no barriers -- MFMA busy 84 % instead of 64 % of the cycles, and the
 // workgroups of an XCD walk the same reference stream in step, so that every line is fetched once per XCD.
 // MFMA-bound (power-capped): 2 * 128 * 512 * dpadh flop per workgroup col-step.
-#include "kernels.h"
+#include "prefilter_dev.h"
 
 namespace vscmi {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 namespace f16p {
 
@@ -39,20 +35,8 @@ constexpr int PF = VSC_F16P_PF;      // register ring: k-steps (PF - 1 in flight
                                      // product build: 4 beats 8 (1314 vs 1284 TFLOP/s thresholded, 1178 vs 1031 k-NN):
                                      // with 8 the register file is full and the compiler shortens the LDS read pipeline
 
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, int voff, char* lds) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds, 16, voff, 0, 0, 0);
-}
-// cache policy of the reference stream (aux bits of the buffer load: 1 = sc0, 2 = nt, 16 = sc1)
-#ifndef VSC_F16P_AUX
-#define VSC_F16P_AUX 0
-#endif
 __device__ __forceinline__ f16x8 bload(__amdgpu_buffer_rsrc_t rs, int voff, int soff) {
-    return __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, VSC_F16P_AUX));
-}
-__device__ __forceinline__ const char* uniform_ptr(const char* p) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return reinterpret_cast<const char*>(((uint64_t)hi << 32) | lo);
+    return __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 0));
 }
 
 // One output tile (128 panel rows x the wave's 64 columns, K = NKC x 128): A fragments from the LDS panel one
@@ -88,26 +72,13 @@ __device__ __forceinline__ void tile_mma(const char* smem, const int (&abase)[8]
     }
 }
 
-// lower edge of the candidate test for an exact threshold t: a pair with exact score >(=) t has fp16 score
-// >= t - eps; the subtraction's own rounding (< 2^-23 relative to the larger operand) is subtracted again
-__device__ __forceinline__ float candidate_edge(float t, float eps) { return (t - eps) - 2.4e-7f * (fabsf(t) + eps); }
-
 // Candidates of one wave tile -> the wave's PRIVATE segment of the candidate list (no atomics, no scans; a
 // shared atomic tail only when the segment is full).  Per 32x32 block one question first (its per-lane
 // maximum is known), then one ballot per accumulator register of the few blocks that hold a candidate.
 //   ROWTHR = false: thr[n] = edge of *radius for the lane's column of block column n (strict test)
 //   ROWTHR = true : rt = the panel's 128 row thresholds, rtmin[m] = smallest of row block m, eps[n] = the
 //                   lane's column bounds (non-strict test: k-NN ties must survive)
-// The lane id, recomputed where it is used (two VALU instructions).  The emission code must not keep per-lane
-// values (row / column offsets of the lane) alive across a tile: the register file is full, the compiler spills
-// them, and a scratch reload in the hit path costs an s_waitcnt vmcnt(0) that also waits for the acknowledgement
-// of every candidate store issued before it (~2 us per hit: half of a tile's time in the early, dense batches).
-__device__ __forceinline__ int lane_now() {
-    int l;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-    return l;
-}
-
+// The lane id is recomputed where it is used (lane_now, prefilter_dev.h: no per-lane value may stay alive across a tile).
 template <bool ROWTHR>
 __device__ __forceinline__ void emit_candidates(const SimF16PArgs& a, const bool (&all)[2], const float (&thr)[2],
                                                 const float (&eps)[2], const float* rt, const float (&rtmin)[4],
@@ -143,87 +114,12 @@ __device__ __forceinline__ void emit_candidates(const SimF16PArgs& a, const bool
                 if (ok == 0ull) continue;
                 const int total = __popcll(ok);
                 int64_t pos;
-                if (count + total <= a.list.seg_cap) {
-                    pos = seg_base + count;
-                    count += total;
-                } else {
-                    // segment full (candidates are not spread evenly): the wave's chunk of the shared tail
-                    if (!tail_take(a.list, total, ln, ext, pos))
-                        continue;
-                }
+                if (!cand_reserve(a.list, seg_base, count, total, ln, ext, pos)) continue;
                 if (mine) {
-                    pos += __builtin_amdgcn_mbcnt_hi((unsigned)(ok >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ok, 0u));
+                    pos += lanes_below(ok);
                     a.list.i[pos] = a.i0 + i;
                     a.list.j[pos] = j;
                 }
-            }
-        }
-}
-
-// The same, block at a time: every lane gathers the candidates among its 16 values of a flagged 32x32 block in a bit
-// mask, the wave takes an exclusive prefix sum of the per-lane counts (ballots of the counts' bit planes) and every
-// lane writes its own candidates behind it.  ~90 instructions per flagged block whatever it holds, against
-// 6 + ~35 per accumulator register with a candidate: 3-4x fewer in the early, dense batches of the schedule (a dozen
-// candidates per block), slightly fewer in the sparse steady state.
-template <bool ROWTHR>
-__device__ __forceinline__ void emit_candidates_blk(const SimF16PArgs& a, const bool (&all)[2], const float (&thr)[2],
-                                                    const float (&eps)[2], const float* rt, const float (&rtmin)[4],
-                                                    int row0, int col0, bool interior, const f32x16 (&acc)[4][2],
-                                                    const float (&bm)[4][2], int64_t seg_base, int& count, TailExt* ext) {
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int n = 0; n < 2; ++n) {
-            const bool blk = all[n] || (ROWTHR ? bm[m][n] >= candidate_edge(rtmin[m], eps[n]) : bm[m][n] > thr[n]);
-            if (!__any(blk)) continue;
-            const int ln = lane_now();  // (live inside the block only, see above)
-            const int hi4 = 4 * (ln >> 5);
-            const int j = col0 + n * 32 + (ln & 31);
-            unsigned mask = 0;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int rb = m * 32 + (r & 3) + 8 * (r >> 2);  // + hi4 = row inside the panel
-                bool cand;
-                if (ROWTHR)
-                    cand = acc[m][n][r] >= candidate_edge(rt[rb + hi4], eps[n]);
-                else
-                    cand = acc[m][n][r] > thr[n];
-                cand |= all[n];
-                // (tiles that reach past the batch or the references drop their padding rows / columns)
-                if (!interior) cand &= row0 + rb + hi4 < a.nq;
-                mask |= cand ? (1u << r) : 0u;
-            }
-            if (!interior && j >= a.nr) mask = 0;
-            const int cnt = __popc(mask);
-            unsigned long long pl = __ballot(cnt & 1);
-            int before = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(pl >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)pl, 0u));
-            int total = __popcll(pl);
-            if (__any(cnt > 1)) {
-#pragma unroll
-                for (int b = 1; b < 5; ++b) {
-                    pl = __ballot((cnt >> b) & 1);
-                    before += (int)__builtin_amdgcn_mbcnt_hi((unsigned)(pl >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)pl, 0u)) << b;
-                    total += __popcll(pl) << b;
-                }
-            }
-            if (total == 0) continue;
-            int64_t pos;
-            if (count + total <= a.list.seg_cap) {
-                pos = seg_base + count;
-                count += total;
-            } else {
-                // segment full (candidates are not spread evenly): the wave's chunk of the shared tail
-                if (!tail_take(a.list, total, ln, ext, pos))
-                    continue;
-            }
-            pos += before;
-            const int ibase = a.i0 + row0 + m * 32 + hi4;
-            while (mask) {
-                const int r = __ffs(mask) - 1;
-                mask &= mask - 1;
-                a.list.i[pos] = ibase + (r & 3) + 8 * (r >> 2);
-                a.list.j[pos] = j;
-                ++pos;
             }
         }
 }
@@ -232,8 +128,10 @@ __device__ __forceinline__ void emit_candidates_blk(const SimF16PArgs& a, const 
 // nothing needs checking and the per-candidate code shrinks to: position = count + (lanes of this register's ballot
 // below me), two buffer stores with a 32-bit offset into the wave's own segment (rs_i / rs_j: buffer resources on the
 // segment, uniform per wave).  Per flagged block: 16 compares + lane id and column (5 VALU); per register that holds a
-// candidate: 4 VALU + 2 stores -- a third of the instructions of the other two forms.  Everything else (edge tiles,
-// segment nearly full, +inf error bounds, the k-NN thresholds) goes through emit_candidates.
+// candidate: 4 VALU + 2 stores -- a third of the instructions of the general form.  Everything else (edge tiles,
+// segment nearly full, +inf error bounds, the k-NN thresholds) goes through emit_candidates.  Measured, pre-filter
+// time of a bench step: 317 ms with emit_candidates everywhere, 304 ms with this fast path; a block-at-a-time emitter
+// (per-lane bit masks + a wave prefix sum) gave 310 ms there and 354 against 348 ms on the k-NN (k = 1), and is gone.
 __device__ __forceinline__ void emit_candidates_seg(const SimF16PArgs& a, const float (&thr)[2], int row0, int col0,
                                                     const f32x16 (&acc)[4][2], const float (&bm)[4][2],
                                                     __amdgpu_buffer_rsrc_t rs_i, __amdgpu_buffer_rsrc_t rs_j, int& count) {
@@ -251,9 +149,7 @@ __device__ __forceinline__ void emit_candidates_seg(const SimF16PArgs& a, const 
                 const unsigned long long hits = __ballot(cand);
                 if (hits == 0ull) continue;
                 if (cand) {
-                    const int off = (count + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(hits >> 32),
-                                                                            __builtin_amdgcn_mbcnt_lo((unsigned)hits, 0u)))
-                                    << 2;
+                    const int off = (count + (int)lanes_below(hits)) << 2;
                     __builtin_amdgcn_raw_buffer_store_b32(ibase + (r & 3) + 8 * (r >> 2), rs_i, off, 0, 0);
                     __builtin_amdgcn_raw_buffer_store_b32(j, rs_j, off, 0, 0);
                 }
@@ -261,14 +157,6 @@ __device__ __forceinline__ void emit_candidates_seg(const SimF16PArgs& a, const 
             }
         }
 }
-
-// 1: one ballot per accumulator register everywhere (emit_candidates); 2: block at a time everywhere; 0: block at a
-// time for the radius search, per register for the k-NN thresholds; 3 (default): emit_candidates_seg on the fast path
-// of the radius search, per register elsewhere.  Pre-filter time of a bench step: 317 ms (1), 310 (0), 304 (3); the
-// k-NN (k = 1) 348 ms (1, 3) against 354 (2).
-#ifndef VSC_F16P_EMIT
-#define VSC_F16P_EMIT 3
-#endif
 
 }  // namespace f16p
 
@@ -309,17 +197,15 @@ __global__ __launch_bounds__(512) void sim_f16p_kernel(SimF16PArgs a) {
     float rtmin[4] = {0.f, 0.f, 0.f, 0.f};
     int panel = blockIdx.x % a.npanel;
     for (;;) {
-        // ---- next work item: a slice of this workgroup's panel, else of the panel with the most left
+        // ---- next work item: a slice of this workgroup's panel, else of the panel with the most left.  (The same loop
+        // as the panel-major branch of sim_i8p.hip, written out in both: as one shared inline function it compiled to
+        // different register allocations of both kernels -- profiles/prefilter_dev_refactor.md.)
         __syncthreads();
         if (wave == 0) {
             int p = panel, s = 0;
             // a launch whose candidate list has overflowed is lost (the host reruns it with larger buffers): stop
             // taking work
-#ifndef VSC_NO_LOST_CHECK
             const bool lost = __hip_atomic_load(a.list.overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-#else
-            const bool lost = false;
-#endif
             for (;;) {
                 if (lost) { p = -1; break; }
                 if (lane == 0) s = atomicAdd(&a.next_slice[p], 1);
@@ -359,7 +245,7 @@ __global__ __launch_bounds__(512) void sim_f16p_kernel(SimF16PArgs a) {
                 const int p = n * 512 + tid;
                 const int kc = p >> 11, row = (p >> 4) & 127, slot = p & 15;
                 const int c = kc * 16 + (slot ^ (row & 15));
-                dma16(qrs, row * ROWB + c * 16, smem + (n * 512 + wave * 64) * 16);
+                dma16(qrs, row * ROWB + c * 16, 0, smem + (n * 512 + wave * 64) * 16);
             }
             // largest row norm of the panel (rows past the batch do not count); k-NN: the row thresholds
             const bool in_batch = tid < PR && panel * PR + tid < a.nq;
@@ -437,11 +323,8 @@ __global__ __launch_bounds__(512) void sim_f16p_kernel(SimF16PArgs a) {
             }
             if (__any(any_blk)) {
                 const bool interior = panel * PR + PR <= a.nq && col0 + 64 <= a.nr;
-                if (VSC_F16P_EMIT == 3 && !ROWTHR && interior && !all[0] && !all[1] && count + 8192 <= a.list.seg_cap)
+                if (!ROWTHR && interior && !all[0] && !all[1] && count + 8192 <= a.list.seg_cap)
                     emit_candidates_seg(a, thr, panel * PR, col0, acc, bm, rs_ci, rs_cj, count);
-                else if (VSC_F16P_EMIT == 2 || (VSC_F16P_EMIT == 0 && !ROWTHR))
-                    emit_candidates_blk<ROWTHR>(a, all, thr, eps, rt_sh, rtmin, panel * PR, col0, interior, acc, bm,
-                                                seg_base, count, &tail_sh[wave]);
                 else
                     emit_candidates<ROWTHR>(a, all, thr, eps, rt_sh, rtmin, panel * PR, col0, interior, acc, bm,
                                             seg_base, count, &tail_sh[wave]);

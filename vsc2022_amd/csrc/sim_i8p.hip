@@ -40,17 +40,11 @@
 // the common path tests against the PANEL's smallest threshold, and only a column block that passes is re-tested
 // per 16-row block against that block's smallest threshold (integer compares only, the arithmetic of 8 thresholds
 // per column block on the rare path instead of 8 per tile on the common one).
-#include "kernels.h"
+#include "prefilter_dev.h"
 
 namespace vscmi {
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
 namespace i8p {
-
-#ifndef VSC_I8P_ABLATE  // timing experiments only (scripts/experiments): 1 = no candidate emission, 2 = no block maxima
-#define VSC_I8P_ABLATE 0  // and no emission either -- both give WRONG results
-#endif
 
 constexpr int PR = F16P_PANEL_ROWS;  // 128
 static_assert(F16P_COL_STEP == 512, "a col-step is 8 waves x 64 columns (or 2 steps of 8 x 32)");
@@ -72,9 +66,6 @@ static_assert((VSC_I8P_PF == 2 || VSC_I8P_PF == 4) && (VSC_I8P_PF2 == 2 || VSC_I
 constexpr int HB = 8;           // 16-row blocks of a 128-row panel (= of a half of a paired wave tile)
 constexpr int AW = 4;           // A operands in registers: a rolling window of AW row blocks (the next AW blocks of the m-major order)
 
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, int voff, char* lds) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds, 16, voff, 0, 0, 0);
-}
 // The reference stream with hand-placed waits (round 3: the loads are opaque to the compiler's s_waitcnt insertion,
 // which otherwise drains the whole stream with vmcnt(0) at the start of every tile -- it loses count of the
 // outstanding loads across the emission branches).  A load's destination must not be touched before ring_wait has
@@ -89,12 +80,11 @@ __device__ __forceinline__ void bload_asm(i32x4& dst, __amdgpu_buffer_rsrc_t rs,
     asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %1, %2, %3 offen offset:%4"
                  : "=&v"(dst) : "v"(voff), "s"(rs), "s"(soff), "n"(OFF) : "memory");
 }
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void gload_asm(f32x4v& dst, const float4* p) {
+__device__ __forceinline__ void gload_asm(f32x4& dst, const float4* p) {
     asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(dst) : "v"(p) : "memory");
 }
 template <int N>
-__device__ __forceinline__ void meta_wait(f32x4v& m) {
+__device__ __forceinline__ void meta_wait(f32x4& m) {
     asm volatile("s_waitcnt vmcnt(%1)" : "+v"(m) : "n"(N));
 }
 template <int N>
@@ -104,11 +94,6 @@ __device__ __forceinline__ void ring_wait(i32x4 (&b)[4]) {
 template <int N>
 __device__ __forceinline__ void ring_wait(i32x4 (&b)[2]) {
     asm volatile("s_waitcnt vmcnt(%2)" : "+v"(b[0]), "+v"(b[1]) : "n"(N));
-}
-__device__ __forceinline__ const char* uniform_ptr(const char* p) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return reinterpret_cast<const char*>(((uint64_t)hi << 32) | lo);
 }
 __device__ __forceinline__ float uniform_f(float x) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x)));
@@ -162,11 +147,9 @@ __device__ __forceinline__ void tile_mma(const char* smem, const int (&abase)[4]
     }
 }
 
-// lower edge of the candidate test for an exact threshold t (as in sim_f16p.hip); t = +inf (the rows of a panel that
-// lie past the batch) stays +inf instead of turning into inf - inf
-__device__ __forceinline__ float candidate_edge(float t, float eps) {
-    return t == INFINITY ? t : (t - eps) - 2.4e-7f * (fabsf(t) + eps);
-}
+// candidate_edge (prefilter_dev.h), except that t = +inf (the rows of a panel that lie past the batch) stays +inf instead
+// of turning into inf - inf: the NaN would pass everything once floor_sat has made an integer threshold of it
+__device__ __forceinline__ float edge_keep_inf(float t, float eps) { return t == INFINITY ? t : candidate_edge(t, eps); }
 // A lower bound of edge / (s_q s_r) from inv = (1 / s_q) (1 / s_r): the few roundings of the quotient are covered by
 // 2e-6 relative; the absolute term keeps a quotient that underflowed to +-0 on the safe side of the integers.
 __device__ __forceinline__ float quotient_low(float edge, float inv) {
@@ -187,14 +170,9 @@ constexpr int PASS_ALL = -2100000000;
 template <bool ROWTHR>
 __device__ __forceinline__ int column_threshold(float t, float eps, float inv) {
     if (!(eps < INFINITY)) return t == INFINITY ? 2100000000 : PASS_ALL;
-    return floor_sat(quotient_low(candidate_edge(t, eps), inv)) - (ROWTHR ? 1 : 0);
+    return floor_sat(quotient_low(edge_keep_inf(t, eps), inv)) - (ROWTHR ? 1 : 0);
 }
 
-__device__ __forceinline__ int lane_now() {
-    int l;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-    return l;
-}
 __device__ __forceinline__ int bperm(int src_lane, int v) { return __builtin_amdgcn_ds_bpermute(src_lane << 2, v); }
 
 // Candidates of one wave tile -> the wave's private segment (no atomics; the wave's chunk of the shared tail when the
@@ -240,16 +218,9 @@ __device__ __forceinline__ void emit_candidates(const SimI8PArgs& a, const int (
                 if (ok == 0ull) continue;
                 const int total = __popcll(ok);
                 int64_t pos;
-                if (count + total <= a.list.seg_cap) {
-                    pos = seg_base + count;
-                    count += total;
-                } else {
-                    // segment full (candidates are not spread evenly): the wave's chunk of the shared tail
-                    if (!tail_take(a.list, total, ln, ext, pos))
-                        continue;
-                }
+                if (!cand_reserve(a.list, seg_base, count, total, ln, ext, pos)) continue;
                 if (mine) {
-                    pos += __builtin_amdgcn_mbcnt_hi((unsigned)(ok >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ok, 0u));
+                    pos += lanes_below(ok);
                     a.list.i[pos] = a.i0 + i;  // (a position when the launch's rows are permuted: the exact stage maps it back)
                     a.list.j[pos] = j;
                 }
@@ -293,9 +264,7 @@ __device__ __forceinline__ void emit_candidates_seg(const SimI8PArgs& a, const i
                 const unsigned long long hits = __ballot(cand);
                 if (hits == 0ull) continue;
                 if (cand) {
-                    const int off = (count + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(hits >> 32),
-                                                                            __builtin_amdgcn_mbcnt_lo((unsigned)hits, 0u)))
-                                    << 2;
+                    const int off = (count + (int)lanes_below(hits)) << 2;
                     __builtin_amdgcn_raw_buffer_store_b32(a.i0 + pbase + m * 16 + r, rs_i, off, 0, 0);
                     __builtin_amdgcn_raw_buffer_store_b32(j, rs_j, off, 0, 0);
                 }
@@ -319,9 +288,6 @@ __global__ __launch_bounds__(512) void sim_i8p_kernel(SimI8PArgs a) {
     __shared__ float rt_sh[ROWTHR ? PRW : 1];
     __shared__ int item_sh[2];
     __shared__ TailExt tail_sh[8];
-#if VSC_I8P_ABLATE
-    __shared__ volatile int ablate_sink;
-#endif
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     constexpr int NK4 = NKC * 4;
@@ -362,7 +328,8 @@ __global__ __launch_bounds__(512) void sim_i8p_kernel(SimI8PArgs a) {
     for (int m = 0; m < MB; ++m) rt16[m] = 0.0f;
     int panel = blockIdx.x % npan;
     for (;;) {
-        // ---- next work item: a slice of this workgroup's panel, else of the panel with the most left
+        // ---- next work item: a slice of this workgroup's panel, else of the panel with the most left (panel-major: the
+        // same loop as sim_f16p.hip's, see there)
         __syncthreads();
         if (wave == 0) {
             int p = panel, s = 0;
@@ -420,7 +387,7 @@ __global__ __launch_bounds__(512) void sim_i8p_kernel(SimI8PArgs a) {
                 const int p = n * 512 + tid;
                 const int kc = p / (PRW * 16), row = (p >> 4) % PRW, slot = p & 15;
                 const int c = kc * 16 + (slot ^ (row & 15));
-                dma16(qrs, row * ROWB + c * 16, smem + (n * 512 + wave * 64) * 16);
+                dma16(qrs, row * ROWB + c * 16, 0, smem + (n * 512 + wave * 64) * 16);
             }
 #pragma unroll
             for (int h = 0; h < HALVES; ++h) {
@@ -475,7 +442,7 @@ __global__ __launch_bounds__(512) void sim_i8p_kernel(SimI8PArgs a) {
             // {1 / s_r, E_r, N_r, N'_r} of the column this lane does the threshold arithmetic of (the table is padded to
             // whole col-steps): issued behind the stream loads of the previous tile, ahead of this tile's -- after the K
             // loop only the CB (PF - 1) stream loads of the next tile are younger
-            f32x4v mt;
+            f32x4 mt;
             gload_asm(mt, a.rmeta + col0 + (lane & (WCOLS - 1)));
             i32x4 acc[MB][CB];
             tile_mma<NKC, MB, CB, PF>(smem, abase, afr, ring, rs, so_tile, so_tile + TPS * TILEB, lane16, acc);
@@ -492,29 +459,12 @@ __global__ __launch_bounds__(512) void sim_i8p_kernel(SimI8PArgs a) {
                 if (!(eps_own[h] < INFINITY) || !(inv_own[h] >= 1e-30f && inv_own[h] < INFINITY)) eps_own[h] = INFINITY;
                 const int t_own = column_threshold<ROWTHR>(ROWTHR ? rt_half[h] : radius, eps_own[h], inv_own[h]);
                 // ... and the thresholds of the columns this lane holds accumulators of
-#if VSC_I8P_ABLATE == 2
-#pragma unroll
-                for (int n = 0; n < CB; ++n) tc[h][n] = t_own;
-#else
 #pragma unroll
                 for (int n = 0; n < CB; ++n) tc[h][n] = bperm(n * 16 + (lane & 15), t_own);
-#endif
             }
-#if VSC_I8P_ABLATE == 2
-#pragma unroll
-            for (int h = 0; h < HALVES; ++h)
-#pragma unroll
-                for (int n = 0; n < CB; ++n) {
-                    // no maxima: one accumulator of every block stands in for the block (keeps the MFMAs alive)
-                    int y = acc[HB * h][n][0];
-                    for (int m = 1; m < HB; ++m) y |= acc[HB * h + m][n][m & 3];
-                    cm[h][n] = y;
-                    any_col |= y == 0x12345678;
-                }
-#else
             // the lane's 32 accumulators of each (128-row panel, column block) (8 row blocks x 4 registers): 16 v_max3
             // each, the four chains advanced together (a chain of dependent v_max3 issues every ~8 cycles, four
-            // independent ones keep the VALU fed).  Measured (round 4, -DVSC_I8P_ABLATE): these maxima + the threshold
+            // independent ones keep the VALU fed).  Measured (round 4, builds without the maxima / without the emission): these maxima + the threshold
             // distribution cost 9 % of the kernel, the emission of this workload's candidates 1 %; starting the second
             // wave of every SIMD 2000-4000 cycles late so that the two waves' epilogues do not coincide: +-0
             {
@@ -538,11 +488,7 @@ __global__ __launch_bounds__(512) void sim_i8p_kernel(SimI8PArgs a) {
                         any_col |= cm[h][n] > tc[h][n];
                     }
             }
-#endif
-#if VSC_I8P_ABLATE
-            if (__any(any_col) && lane == 0) ablate_sink = col0;  // (keeps the accumulators alive)
-#endif
-            if (VSC_I8P_ABLATE == 0 && __any(any_col)) {
+            if (__any(any_col)) {
                 const bool interior = panel * PRW + PRW <= a.nq && col0 + WCOLS <= a.nr;
                 if (interior && count + 8192 <= a.list.seg_cap) {
                     emit_candidates_seg<ROWTHR, MB, CB, 0>(a, tc[0], cm[0], rt16, eps_own[0], inv_own[0], panel * PRW, col0, acc,
@@ -568,9 +514,6 @@ __global__ __launch_bounds__(512) void sim_i8p_kernel(SimI8PArgs a) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     tail_close(a.list, lane, &tail_sh[wave]);
-#if VSC_I8P_ABLATE
-    if (ablate_sink == 0x7fffffff) count = -1;
-#endif
     if (lane == 0) a.list.seg_count[seg] = count;
 }
 

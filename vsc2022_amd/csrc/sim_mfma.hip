@@ -16,12 +16,9 @@
 #include <cfloat>
 #include <cstdlib>
 
-#include "kernels.h"
+#include "prefilter_dev.h"
 
 namespace vscmi {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BM = 128;
 constexpr int BN = 128;
@@ -30,14 +27,7 @@ constexpr int TILE_BYTES = BM * BK * 4;      // 16 KiB per operand per stage
 constexpr int STAGE_BYTES = 2 * TILE_BYTES;  // A + B
 constexpr int GEMM_LDS = 2 * STAGE_BYTES;    // 64 KiB
 
-// LDS-DMA of one 16-byte piece per lane: buffer_load_dwordx4 ... lds.  The buffer descriptor is
-// wave-uniform (tile base), the per-lane part is a 32-bit byte offset, the K-tile advance rides in
-// the scalar offset: no 64-bit address arithmetic per issue.
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, int voff, int soff, char* lds) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds, 16, voff,
-                                             soff, 0, 0);
-}
-
+// (operand tiles arrive by LDS-DMA, one 16-byte piece per lane: dma16, prefilter_dev.h)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t tile_rsrc(const float* base, int dpad) {
     // make the (already wave-uniform) base provably uniform so the descriptor lives in SGPRs
     const uint64_t p = reinterpret_cast<uint64_t>(base);
