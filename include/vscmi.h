@@ -326,6 +326,30 @@ typedef struct vsc_tn_params {
 int vsc_tn_create(const float* qfeat, const int64_t* q_off, int64_t n_qvid, const float* rfeat,
                   const int64_t* r_off, int64_t n_rvid, int dim, int feat_mem, int device,
                   vsc_tn_ctx_t** out);
+/* The same with a codec for the REFERENCE rows, fixed for the life of the context; vsc_tn_create means VSC_CODEC_FLAT
+ * with fp32 references in feat_mem.  The query side is fp32 (qfeat, in feat_mem) under both codecs.
+ *
+ * rfeat / ref_f16 / ref_mem: the reference rows [total_r_rows][dim], in ref_mem (VSC_MEM_HOST / VSC_MEM_DEVICE); fp32
+ * when ref_f16 == 0, else IEEE half floats given as uint16 bit patterns, as vsc_index_add_f16 takes them.
+ *
+ * VSC_CODEC_SQFP16.  The contract of the index codec (vsc_index_create_codec), word for word: a context whose
+ * references are the rows X behaves as the Flat context on
+ *     dec(X) = the rows rounded to IEEE half floats (round to nearest even, subnormals kept) and converted back:
+ * vsc_tn_localize returns that context's boxes, box counts and MaxSim score BITS, vsc_tn_similarity its matrix BITS;
+ * vsc_tn_set_queries and vsc_tn_set_stream mean what they mean there.  Rows that are already half floats decode to
+ * themselves.  The reference rows live once in HBM, as half floats ([rows + slack][dim padded to 64], natural order:
+ * 2 bytes per padded element instead of 4); the packed fp32 image of a Flat context is never allocated, and half rows
+ * reach the store in staging chunks of their own size, never as fp32.  The kernels convert the halves in registers
+ * (exactly) and run the same ascending-k fp32 chain.
+ * A reference row holding NaN, +-inf or a value beyond +-65504 makes the call fail with VSC_ERR_INVALID: *out is NULL
+ * and nothing stays allocated.
+ * VSC_CODEC_FLAT with ref_f16 != 0 is the Flat context of the upcast rows. */
+int vsc_tn_create_codec(const float* qfeat, const int64_t* q_off, int64_t n_qvid, const void* rfeat, int ref_f16,
+                        const int64_t* r_off, int64_t n_rvid, int dim, int feat_mem, int ref_mem, int codec,
+                        int device, vsc_tn_ctx_t** out);
+/* Bytes the context asked the device for to hold its reference descriptor rows (the counterpart of the index's
+ * read-only "ref_bytes"): rows rounded up as the kernels need them x padded dim x 4 (Flat) or 2 (SQfp16). */
+int64_t vsc_tn_ref_bytes(const vsc_tn_ctx_t* ctx);
 int vsc_tn_destroy(vsc_tn_ctx_t* ctx);
 /* As vsc_index_set_stream, for a localisation context. */
 int vsc_tn_set_stream(vsc_tn_ctx_t* ctx, void* hip_stream, int own);

@@ -374,7 +374,7 @@ static int tn_run_buckets(TnPairArgs base, const std::vector<int32_t>& lqs, cons
             for (int64_t x = c0; x < c0 + cn; ++x) {
                 const int32_t p = B.work[(size_t)x];
                 const double lq = lqs[(size_t)p], lr = lrs[(size_t)p];
-                bytes += fused ? 4.0 * base.dpad * (lq + lr) : 4.0 * lq * lr;
+                bytes += fused ? base.dpad * (4.0 * lq + (base.rfeat_h ? 2.0 : 4.0) * lr) : 4.0 * lq * lr;
                 bytes += 4.0 + 20.0 * VSC_TN_MAX_BOXES;
             }
             AuxTimer tm;
@@ -393,9 +393,14 @@ static int tn_run_buckets(TnPairArgs base, const std::vector<int32_t>& lqs, cons
 
 struct vsc_tn_ctx {
     int device = 0, dim = 0, dpad = 0;
+    // VSC_CODEC_FLAT: `rfeat` holds the packed fp32 reference rows.  VSC_CODEC_SQFP16: `rfeat` is never allocated; the
+    // rows live once, as half floats, in `rfeat_h` ([r_rows][dpad], natural k order, zero padded) and the kernels
+    // convert them in registers.  The query side is packed fp32 either way
+    int codec = VSC_CODEC_FLAT;
+    int64_t ref_bytes = 0;  // bytes asked for the reference rows (vsc_tn_ref_bytes)
     int64_t n_qvid = 0, n_rvid = 0;
     std::vector<int64_t> q_off, r_off;  // host copies
-    DevBuf qfeat, rfeat, d_qoff, d_roff;
+    DevBuf qfeat, rfeat, rfeat_h, d_qoff, d_roff;
     DevBuf d_pq, d_pr, d_work, d_nbox, d_boxes, d_bmax, slab, sims;
     Workspace ws;
     hipStream_t stream = nullptr;      // own_stream, or the caller's (vsc_tn_set_stream)
@@ -416,11 +421,71 @@ int vsc_tn_set_stream(vsc_tn_ctx_t* c, void* hip_stream, int own) {
     return VSC_OK;
 }
 
-int vsc_tn_create(const float* qfeat, const int64_t* q_off, int64_t n_qvid, const float* rfeat,
-                  const int64_t* r_off, int64_t n_rvid, int dim, int feat_mem, int device,
-                  vsc_tn_ctx_t** out) {
-    if (!out || dim <= 0 || n_qvid < 0 || n_rvid < 0 || !q_off || !r_off) {
-        set_error("vsc_tn_create: invalid argument");
+// Flat context, reference rows handed over as half floats: decoded in bounded chunks (ws.dec) and packed like fp32
+// rows -- the context of the upcast array.
+static int tn_pack_f16_rows(vsc_tn_ctx* c, const uint16_t* x, int64_t n, int mem, float* dst, int64_t rows_out) {
+    if (n == 0) return launch_pack_rows(nullptr, 0, c->dim, dst, rows_out, c->dpad, c->stream);
+    Workspace& ws = c->ws;
+    const int64_t chunk_rows = std::max<int64_t>(1, (int64_t)(64ll << 20) / ((int64_t)c->dim * 4));
+    VSC_TRY(ws.dec.reserve((size_t)std::min(chunk_rows, n) * c->dim * 4));
+    if (mem != VSC_MEM_DEVICE) VSC_TRY(ws.stage.reserve((size_t)std::min(chunk_rows, n) * c->dim * 2));
+    for (int64_t r0 = 0; r0 < n; r0 += chunk_rows) {
+        const int64_t rows = std::min(chunk_rows, n - r0);
+        const uint16_t* src = x + r0 * c->dim;
+        if (mem != VSC_MEM_DEVICE) {
+            VSC_HIP(hipMemcpyAsync(ws.stage.p, src, (size_t)rows * c->dim * 2, hipMemcpyHostToDevice, c->stream));
+            src = ws.stage.as<uint16_t>();
+        }
+        VSC_TRY(launch_half_to_float(reinterpret_cast<const _Float16*>(src), rows * c->dim, ws.dec.as<float>(), c->stream));
+        VSC_TRY(launch_pack_rows(ws.dec.as<float>(), rows, c->dim, dst + r0 * c->dpad, r0 + rows == n ? rows_out - r0 : rows, c->dpad, c->stream));
+        VSC_HIP(hipStreamSynchronize(c->stream));  // the buffers are reused
+    }
+    return VSC_OK;
+}
+
+// SQfp16 context: the reference store from fp32 or fp16 rows, by the index codec's encoder (codec_f16.hip: round to
+// nearest even, subnormals kept, natural layout).  All r_rows rows are written, those from n on as zeros.  Host sources
+// are staged in chunks of their own element size: no fp32 image of the rows exists at any time.  The encoder's per-row
+// norm bounds are of no use here and go to a scratch buffer of one chunk.
+static int tn_store_rows(vsc_tn_ctx* c, const void* x, bool src16, int64_t n, int mem, int64_t r_rows) {
+    const size_t esz = src16 ? 2 : 4;
+    Workspace& ws = c->ws;
+    VSC_TRY(ws.flag.reserve(16));
+    int* d_bad = ws.flag.as<int>();
+    VSC_HIP(hipMemsetAsync(d_bad, 0, sizeof(int), c->stream));
+    _Float16* image = c->rfeat_h.as<_Float16>();
+    const int64_t chunk_rows = std::max<int64_t>(ROW_PAD, (int64_t)(256ll << 20) / ((int64_t)c->dim * (int64_t)esz));
+    VSC_TRY(ws.qn.reserve((size_t)std::min(chunk_rows, r_rows) * 4));
+    const bool host = mem != VSC_MEM_DEVICE;
+    if (host && n > 0) VSC_TRY(ws.stage.reserve((size_t)std::min(chunk_rows, n) * c->dim * esz));
+    for (int64_t r0 = 0; r0 < r_rows; r0 += chunk_rows) {
+        const int64_t rows_out = std::min(chunk_rows, r_rows - r0);
+        const int64_t rows = std::max<int64_t>(0, std::min(rows_out, n - r0));  // source rows of the chunk
+        const void* src = rows ? static_cast<const char*>(x) + (size_t)r0 * c->dim * esz : nullptr;
+        if (host && rows) {
+            VSC_HIP(hipMemcpyAsync(ws.stage.p, src, (size_t)rows * c->dim * esz, hipMemcpyHostToDevice, c->stream));
+            src = ws.stage.p;
+        }
+        VSC_TRY(launch_encode_rows(src, src16, rows, c->dim, image, ws.qn.as<float>(), r0, rows_out, c->dpad, false, d_bad, c->stream));
+        if (host) VSC_HIP(hipStreamSynchronize(c->stream));  // the staging buffer is reused
+    }
+    int bad = 0;
+    VSC_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    VSC_HIP(hipStreamSynchronize(c->stream));
+    if (bad) {
+        set_error("vsc_tn_create_codec: a reference row holds NaN, +-inf or a value beyond +-65504, which the SQfp16 codec cannot store");
+        return VSC_ERR_INVALID;
+    }
+    return VSC_OK;
+}
+
+int vsc_tn_create_codec(const float* qfeat, const int64_t* q_off, int64_t n_qvid, const void* rfeat, int ref_f16,
+                        const int64_t* r_off, int64_t n_rvid, int dim, int feat_mem, int ref_mem, int codec, int device,
+                        vsc_tn_ctx_t** out) {
+    if (out) *out = nullptr;
+    if (!out || dim <= 0 || n_qvid < 0 || n_rvid < 0 || !q_off || !r_off || (codec != VSC_CODEC_FLAT && codec != VSC_CODEC_SQFP16) ||
+        (n_rvid > 0 && r_off[n_rvid] > 0 && !rfeat)) {
+        set_error("vsc_tn_create_codec: invalid argument");
         return VSC_ERR_INVALID;
     }
     VSC_TRY(check_device(device));
@@ -429,6 +494,7 @@ int vsc_tn_create(const float* qfeat, const int64_t* q_off, int64_t n_qvid, cons
     c->device = device;
     c->dim = dim;
     c->dpad = round_up(dim, K_PAD);
+    c->codec = codec;
     c->n_qvid = n_qvid;
     c->n_rvid = n_rvid;
     c->q_off.assign(q_off, q_off + n_qvid + 1);
@@ -448,20 +514,38 @@ int vsc_tn_create(const float* qfeat, const int64_t* q_off, int64_t n_qvid, cons
     // +32 rows of slack: the 32-row MFMA blocks of the last video read past its end
     const int64_t q_rows = round_up64(nq + 32, ROW_PAD), r_rows = round_up64(nr + 32, ROW_PAD);
     if ((rc = c->qfeat.reserve((size_t)q_rows * c->dpad * 4)) != VSC_OK) return fail(rc);
-    if ((rc = c->rfeat.reserve((size_t)r_rows * c->dpad * 4)) != VSC_OK) return fail(rc);
     if ((rc = pack_into(qfeat, nq, dim, feat_mem, c->qfeat.as<float>(), q_rows, c->dpad, c->ws, c->stream)) != VSC_OK) return fail(rc);
-    if ((rc = pack_into(rfeat, nr, dim, feat_mem, c->rfeat.as<float>(), r_rows, c->dpad, c->ws, c->stream)) != VSC_OK) return fail(rc);
+    if (codec == VSC_CODEC_SQFP16) {
+        c->ref_bytes = r_rows * c->dpad * 2;
+        if ((rc = c->rfeat_h.reserve((size_t)c->ref_bytes)) != VSC_OK) return fail(rc);
+        if ((rc = tn_store_rows(c, rfeat, ref_f16 != 0, nr, ref_mem, r_rows)) != VSC_OK) return fail(rc);
+        c->ws.qn.release();  // (scratch of the encoder)
+    } else {
+        c->ref_bytes = r_rows * c->dpad * 4;
+        if ((rc = c->rfeat.reserve((size_t)c->ref_bytes)) != VSC_OK) return fail(rc);
+        if (ref_f16) rc = tn_pack_f16_rows(c, static_cast<const uint16_t*>(rfeat), nr, ref_mem, c->rfeat.as<float>(), r_rows);
+        else rc = pack_into(static_cast<const float*>(rfeat), nr, dim, ref_mem, c->rfeat.as<float>(), r_rows, c->dpad, c->ws, c->stream);
+        if (rc != VSC_OK) return fail(rc);
+    }
     if ((rc = c->d_qoff.reserve((size_t)(n_qvid + 1) * 8)) != VSC_OK) return fail(rc);
     if ((rc = c->d_roff.reserve((size_t)(n_rvid + 1) * 8)) != VSC_OK) return fail(rc);
     if (hipMemcpyAsync(c->d_qoff.p, c->q_off.data(), (size_t)(n_qvid + 1) * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
         hipMemcpyAsync(c->d_roff.p, c->r_off.data(), (size_t)(n_rvid + 1) * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess) {
-        set_error("vsc_tn_create: offset upload failed");
+        set_error("vsc_tn_create_codec: offset upload failed");
         return fail(VSC_ERR_HIP);
     }
     *out = c;
     return VSC_OK;
 }
+
+int vsc_tn_create(const float* qfeat, const int64_t* q_off, int64_t n_qvid, const float* rfeat,
+                  const int64_t* r_off, int64_t n_rvid, int dim, int feat_mem, int device,
+                  vsc_tn_ctx_t** out) {
+    return vsc_tn_create_codec(qfeat, q_off, n_qvid, rfeat, 0, r_off, n_rvid, dim, feat_mem, feat_mem, VSC_CODEC_FLAT, device, out);
+}
+
+int64_t vsc_tn_ref_bytes(const vsc_tn_ctx_t* c) { return c ? c->ref_bytes : 0; }
 
 int vsc_tn_set_queries(vsc_tn_ctx_t* c, const float* qfeat, const int64_t* q_off, int64_t n_qvid, int feat_mem) {
     if (!c || n_qvid < 0 || !q_off || (n_qvid > 0 && q_off[n_qvid] > 0 && !qfeat)) {
@@ -501,7 +585,7 @@ int vsc_tn_destroy(vsc_tn_ctx_t* c) {
     (void)hipSetDevice(c->device);
     if (c->stream == c->own_stream) { if (c->own_stream) (void)hipStreamSynchronize(c->own_stream); }
     else (void)hipDeviceSynchronize();
-    c->qfeat.release(); c->rfeat.release(); c->d_qoff.release(); c->d_roff.release();
+    c->qfeat.release(); c->rfeat.release(); c->rfeat_h.release(); c->d_qoff.release(); c->d_roff.release();
     c->d_pq.release(); c->d_pr.release(); c->d_work.release(); c->d_nbox.release();
     c->d_boxes.release(); c->d_bmax.release(); c->slab.release(); c->sims.release();
     c->ws.release();
@@ -568,6 +652,7 @@ int vsc_tn_localize(vsc_tn_ctx_t* c, const int32_t* pair_q, const int32_t* pair_
     memset(&base, 0, sizeof(base));
     base.qfeat = c->qfeat.as<float>();
     base.rfeat = c->rfeat.as<float>();
+    base.rfeat_h = c->rfeat_h.as<_Float16>();  // (nullptr in a Flat context)
     base.q_off = c->d_qoff.as<int64_t>();
     base.r_off = c->d_roff.as<int64_t>();
     base.dpad = c->dpad;
@@ -662,7 +747,7 @@ int vsc_tn_similarity(vsc_tn_ctx_t* c, int32_t q_vid, int32_t r_vid, float bias,
     VSC_HIP(hipSetDevice(c->device));
     VSC_TRY(c->sims.reserve((size_t)lq * lr * 4));
     TnSimsArgs a{c->qfeat.as<float>(), c->rfeat.as<float>(), c->q_off[q_vid], c->r_off[r_vid], (int)lq, (int)lr,
-                 c->dpad, bias, c->sims.as<float>()};
+                 c->dpad, bias, c->sims.as<float>(), c->rfeat_h.as<_Float16>()};
     VSC_TRY(launch_tn_sims(a, c->stream));
     VSC_HIP(hipMemcpyAsync(out, c->sims.p, (size_t)lq * lr * 4, hipMemcpyDeviceToHost, c->stream));
     VSC_HIP(hipStreamSynchronize(c->stream));

@@ -151,8 +151,14 @@ struct TnPairArgs {
     const float* sims_in; const int64_t* sims_off; const int32_t* sims_lq; const int32_t* sims_lr;
     // over-long videos: per-workgroup working state in HBM (state_bytes each) instead of LDS; nullptr = LDS
     char* state; int64_t state_bytes;
+    // SQfp16 context: the reference rows as half floats, [rows][dpad] in natural k order, instead of rfeat (nullptr:
+    // rfeat, packed fp32).  The query side is packed fp32 either way
+    const _Float16* rfeat_h;
 };
-struct TnSimsArgs { const float* qfeat; const float* rfeat; int64_t qrow0, rrow0; int lq, lr, dpad; float bias; float* out; };
+struct TnSimsArgs {
+    const float* qfeat; const float* rfeat; int64_t qrow0, rrow0; int lq, lr, dpad; float bias; float* out;
+    const _Float16* rfeat_h;  // as in TnPairArgs
+};
 
 int launch_sim_thresh(const SimThreshArgs&, hipStream_t);
 int launch_sim_f16(const SimF16Args&, hipStream_t);

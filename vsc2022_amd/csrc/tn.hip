@@ -26,6 +26,35 @@ namespace vscmi {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+// Where the similarity tile reads a reference row from (template parameter RH16 of the kernels below).
+//   false: the packed fp32 rows (vscmi_common.h: k-interleaved) -- the 16-byte load at float offset hi * 4 of k-group g
+//          hands lane half `hi` its k = 8 g + 2 s + hi, s = 0..3.
+//   true:  the half-float store of an SQfp16 context ([rows][dpad] halves, natural k order) -- both lane halves load
+//          the whole 16-byte piece g; half `hi` keeps its even (hi = 0) or odd (hi = 1) elements, i.e. the low or the
+//          high 16 bits of each of the four words, and converts them with the hardware cvt (exact).  The same values
+//          in the same order reach the MFMA chain as from the packed fp32 image of the decoded rows.  One load
+//          instruction per piece, as before (the phase waits on row loads), for half the bytes; the 4 shifts + 4 cvt
+//          per piece issue beside the 4 or 8 MFMAs (64 cycles each) of the k-group.
+template <bool RH16> struct TnRef;
+template <> struct TnRef<false> {
+    typedef float T;
+    template <class A> static __device__ __forceinline__ const T* row(const A& a, int64_t r, int hi) { return a.rfeat + r * a.dpad + hi * 4; }
+};
+template <> struct TnRef<true> {
+    typedef _Float16 T;
+    template <class A> static __device__ __forceinline__ const T* row(const A& a, int64_t r, int) { return a.rfeat_h + r * a.dpad; }
+};
+__device__ __forceinline__ f32x4 tn_ref_piece(const float* p, int g, int) { return *reinterpret_cast<const f32x4*>(p + g * 8); }
+__device__ __forceinline__ f32x4 tn_ref_piece(const _Float16* p, int g, int hi) {
+    const u32x4 w = *reinterpret_cast<const u32x4*>(p + g * 8);
+    const int sh = hi * 16;
+    f32x4 v;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) v[s] = (float)__builtin_bit_cast(_Float16, (unsigned short)(w[s] >> sh));
+    return v;
+}
 
 
 // IDX: type of the stored reference / node indices -- short while the working state lives in LDS (<= 32767 nodes
@@ -124,7 +153,7 @@ __device__ unsigned long long tn_prof[8];
 #define TN_T(k) do {} while (0)
 #endif
 
-template <class IDX, bool GSTATE>
+template <class IDX, bool GSTATE, bool RH16>
 __global__ __launch_bounds__(64) void tn_pair_kernel(TnPairArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem_lds[];
     // working state: LDS, or this workgroup's slice of the HBM state slab (over-long videos; a single wavefront per
@@ -207,8 +236,8 @@ __global__ __launch_bounds__(64) void tn_pair_kernel(TnPairArgs a) {
                 // rows past the video end read the (padded) neighbour rows; their results are dropped
                 const bool two = rb + 32 < lr;
                 const float* ap = a.qfeat + (qrow0 + qb + l31) * a.dpad + hi * 4;
-                const float* bp0 = a.rfeat + (rrow0 + rb + l31) * a.dpad + hi * 4;
-                const float* bp1 = bp0 + (two ? 32 * (int64_t)a.dpad : 0);
+                const typename TnRef<RH16>::T* bp0 = TnRef<RH16>::row(a, rrow0 + rb + l31, hi);
+                const typename TnRef<RH16>::T* bp1 = bp0 + (two ? 32 * (int64_t)a.dpad : 0);
                 f32x16 acc0, acc1;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc0[r] = acc1[r] = 0.0f;
@@ -216,8 +245,8 @@ __global__ __launch_bounds__(64) void tn_pair_kernel(TnPairArgs a) {
 #pragma unroll 4
                     for (int g = 0; g < nkg; ++g) {
                         const f32x4 av = *reinterpret_cast<const f32x4*>(ap + g * 8);
-                        const f32x4 bv0 = *reinterpret_cast<const f32x4*>(bp0 + g * 8);
-                        const f32x4 bv1 = *reinterpret_cast<const f32x4*>(bp1 + g * 8);
+                        const f32x4 bv0 = tn_ref_piece(bp0, g, hi);
+                        const f32x4 bv1 = tn_ref_piece(bp1, g, hi);
 #pragma unroll
                         for (int s = 0; s < 4; ++s) {
                             acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], bv0[s], acc0, 0, 0, 0);
@@ -228,7 +257,7 @@ __global__ __launch_bounds__(64) void tn_pair_kernel(TnPairArgs a) {
 #pragma unroll 4
                     for (int g = 0; g < nkg; ++g) {
                         const f32x4 av = *reinterpret_cast<const f32x4*>(ap + g * 8);
-                        const f32x4 bv = *reinterpret_cast<const f32x4*>(bp0 + g * 8);
+                        const f32x4 bv = tn_ref_piece(bp0, g, hi);
 #pragma unroll
                         for (int s = 0; s < 4; ++s)
                             acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], bv[s], acc0, 0, 0, 0);
@@ -720,32 +749,38 @@ size_t tn_state_bytes_host(int max_lq, int top_cap, int ms, int idx_bytes) {
     return b;
 }
 
-int launch_tn_pairs(const TnPairArgs& a, size_t lds_bytes, hipStream_t stream) {
-    if (a.n_work <= 0) return VSC_OK;
-    static PerDeviceOnce once;
+template <bool RH16>
+static int launch_tn_pairs_from(const TnPairArgs& a, size_t lds_bytes, hipStream_t stream) {
+    static PerDeviceOnce once;  // (one per reference source: the attribute belongs to the instantiation)
     if (a.state) {  // over-long videos: state in the HBM slab, 32-bit indices
-        hipLaunchKernelGGL((tn_pair_kernel<int, true>), dim3((unsigned)a.n_work), dim3(64), 0, stream, a);
+        hipLaunchKernelGGL((tn_pair_kernel<int, true, RH16>), dim3((unsigned)a.n_work), dim3(64), 0, stream, a);
         VSC_HIP(hipGetLastError());
         return VSC_OK;
     }
     if (once.first()) {
-        VSC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&tn_pair_kernel<short, false>),
+        VSC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&tn_pair_kernel<short, false, RH16>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
         once.commit();
     }
-    hipLaunchKernelGGL((tn_pair_kernel<short, false>), dim3((unsigned)a.n_work), dim3(64), lds_bytes, stream, a);
+    hipLaunchKernelGGL((tn_pair_kernel<short, false, RH16>), dim3((unsigned)a.n_work), dim3(64), lds_bytes, stream, a);
     VSC_HIP(hipGetLastError());
     return VSC_OK;
 }
 
+int launch_tn_pairs(const TnPairArgs& a, size_t lds_bytes, hipStream_t stream) {
+    if (a.n_work <= 0) return VSC_OK;
+    // (forward_sim mode reads no descriptors: rfeat_h is never set there)
+    return a.rfeat_h ? launch_tn_pairs_from<true>(a, lds_bytes, stream) : launch_tn_pairs_from<false>(a, lds_bytes, stream);
+}
+
 // LocalizationWithMetadata.similarity (vsc/baseline/localization.py:33-36,48-54) for one pair:
 // out[lq][lr] = q.feature @ r.feature.T + bias, one 32x32 block per wavefront.
-
+template <bool RH16>
 __global__ __launch_bounds__(64) void tn_sims_kernel(TnSimsArgs a) {
     const int lane = threadIdx.x, hi = lane >> 5, l31 = lane & 31;
     const int qb = blockIdx.y * 32, rb = blockIdx.x * 32;
     const float* ap = a.qfeat + (a.qrow0 + qb + l31) * a.dpad + hi * 4;
-    const float* bp = a.rfeat + (a.rrow0 + rb + l31) * a.dpad + hi * 4;
+    const typename TnRef<RH16>::T* bp = TnRef<RH16>::row(a, a.rrow0 + rb + l31, hi);
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
@@ -753,7 +788,7 @@ __global__ __launch_bounds__(64) void tn_sims_kernel(TnSimsArgs a) {
 #pragma unroll 4
     for (int g = 0; g < nkg; ++g) {
         const f32x4 av = *reinterpret_cast<const f32x4*>(ap + g * 8);
-        const f32x4 bv = *reinterpret_cast<const f32x4*>(bp + g * 8);
+        const f32x4 bv = tn_ref_piece(bp, g, hi);
 #pragma unroll
         for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], bv[s], acc, 0, 0, 0);
     }
@@ -767,7 +802,9 @@ __global__ __launch_bounds__(64) void tn_sims_kernel(TnSimsArgs a) {
 
 int launch_tn_sims(const TnSimsArgs& a, hipStream_t stream) {
     if (a.lq <= 0 || a.lr <= 0) return VSC_OK;
-    hipLaunchKernelGGL(tn_sims_kernel, dim3((a.lr + 31) / 32, (a.lq + 31) / 32), dim3(64), 0, stream, a);
+    const dim3 grid((a.lr + 31) / 32, (a.lq + 31) / 32);
+    if (a.rfeat_h) hipLaunchKernelGGL(tn_sims_kernel<true>, grid, dim3(64), 0, stream, a);
+    else hipLaunchKernelGGL(tn_sims_kernel<false>, grid, dim3(64), 0, stream, a);
     VSC_HIP(hipGetLastError());
     return VSC_OK;
 }

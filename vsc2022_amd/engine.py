@@ -154,14 +154,19 @@ class DeviceMatcher:
     *_off: int64 numpy row offsets per video.
     """
 
-    def __init__(self, ref_feats, r_off: np.ndarray, device: Optional[int] = None, tn_ref_feats=None, codec: str = "Flat"):
+    def __init__(self, ref_feats, r_off: np.ndarray, device: Optional[int] = None, tn_ref_feats=None, codec: str = "Flat",
+                 tn_codec: str = "Flat"):
         """codec: how the search index (and the column index of the column-sharded mode) stores the reference rows
         ("Flat" / "SQfp16", vsc.index.FlatIndex).  The codec belongs to the index: the Temporal-Network context keeps its
-        own fp32 copy of the descriptors it is given, as localisation does in the reference.
+        own copy of the descriptors it is given, as localisation does in the reference.
+        tn_codec: how that context stores them: "Flat" as fp32, "SQfp16" once, as half floats (include/vscmi.h,
+        vsc_tn_create_codec: the results are those of the fp32 context on the rows rounded to float16).
 
         tn_ref_feats: reference rows the ALIGNER sees when they differ from the rows that are searched
         (vsc/baseline/sscd_baseline.py:128-135: without score normalisation the reference searches the descriptors as they
         are and localises on their L2-normalised copies)."""
+        self._tn_codec_id = _lib.codec_id(tn_codec)  # (NotImplementedError for an unknown string before any device is needed)
+        self.tn_codec = tn_codec
         self.device = _lib.default_device() if device is None else int(device)
         self.tdev = torch.device("cuda", self.device)
         torch.cuda.set_device(self.tdev)
@@ -212,10 +217,10 @@ class DeviceMatcher:
             return
         torch.cuda.synchronize(self.tdev)  # (once: a fresh context packs its rows on its own stream, bound below)
         ctx = ctypes.c_void_p()
-        _lib.check(_lib.lib().vsc_tn_create(
-            _dev_ptr(self.tn_q_feats), self.q_off.ctypes.data, self.n_qvid, _dev_ptr(self.tn_ref_feats),
-            self.r_off.ctypes.data, self.n_rvid, int(self.tn_ref_feats.shape[1]), _lib.MEM_DEVICE, self.device,
-            ctypes.byref(ctx)))
+        _lib.check(_lib.lib().vsc_tn_create_codec(
+            _dev_ptr(self.tn_q_feats), self.q_off.ctypes.data, self.n_qvid, _dev_ptr(self.tn_ref_feats), 0,
+            self.r_off.ctypes.data, self.n_rvid, int(self.tn_ref_feats.shape[1]), _lib.MEM_DEVICE, _lib.MEM_DEVICE,
+            self._tn_codec_id, self.device, ctypes.byref(ctx)))
         self._tn = ctx
         self._tn_stream = None
         self._order()

@@ -39,7 +39,12 @@ class Localization(abc.ABC):
 class LocalizationWithMetadata(Localization):
     """Keeps the descriptors of both sides (by video id) -- here: resident in HBM."""
 
-    def __init__(self, queries: List[VideoFeature], refs: List[VideoFeature], device=None):
+    def __init__(self, queries: List[VideoFeature], refs: List[VideoFeature], device=None, ref_codec: str = "Flat"):
+        """ref_codec: how the context stores the reference descriptors ("Flat" / "SQfp16", as vsc.index.VideoIndex).
+        "SQfp16" keeps them once, as half floats: every result is that of the same class on the references rounded to
+        float16 and converted back.  References whose `feature` arrays are all float16 are handed over as half rows."""
+        self._ref_codec_id = _lib.codec_id(ref_codec)  # NotImplementedError for every other string, device or not
+        self.ref_codec = ref_codec
         # id -> VideoFeature; a repeated id keeps its last occurrence, as a dict does in the reference
         self.queries: Dict[object, VideoFeature] = {v.video_id: v for v in queries}
         self.refs: Dict[object, VideoFeature] = {v.video_id: v for v in refs}
@@ -52,14 +57,24 @@ class LocalizationWithMetadata(Localization):
 
     def _upload(self):
         q_layout, r_layout = VideoLayout(self._q_videos), VideoLayout(self._r_videos)
-        q_rows, r_rows = VideoLayout.features(self._q_videos), VideoLayout.features(self._r_videos)
+        q_rows = VideoLayout.features(self._q_videos)
+        r_half = len(self._r_videos) > 0 and all(np.asarray(v.feature).dtype == np.float16 for v in self._r_videos)
+        if r_half:  # (the rows go down as they are: 2 bytes per element on the host, in staging and in an SQfp16 store)
+            r_rows = np.ascontiguousarray(np.concatenate([np.asarray(v.feature) for v in self._r_videos], axis=0))
+        else:
+            r_rows = VideoLayout.features(self._r_videos)
         if q_rows.size and r_rows.size and q_rows.shape[1] != r_rows.shape[1]:
             raise ValueError("query and reference descriptors differ in dimension")
         dim = q_rows.shape[1] if q_rows.size else (r_rows.shape[1] if r_rows.size else 1)
-        _lib.check(_lib.lib().vsc_tn_create(
+        _lib.check(_lib.lib().vsc_tn_create_codec(
             q_rows.ctypes.data if q_rows.size else None, q_layout.offsets.ctypes.data, len(self._q_videos),
-            r_rows.ctypes.data if r_rows.size else None, r_layout.offsets.ctypes.data, len(self._r_videos),
-            int(dim), _lib.MEM_HOST, self.device, ctypes.byref(self._ctx)))
+            r_rows.ctypes.data if r_rows.size else None, int(r_half), r_layout.offsets.ctypes.data, len(self._r_videos),
+            int(dim), _lib.MEM_HOST, _lib.MEM_HOST, self._ref_codec_id, self.device, ctypes.byref(self._ctx)))
+
+    @property
+    def ref_bytes(self) -> int:
+        """Bytes of HBM the context holds for the reference descriptor rows."""
+        return int(_lib.lib().vsc_tn_ref_bytes(self._ctx))
 
     def __del__(self):
         ctx = getattr(self, "_ctx", None)
@@ -86,8 +101,8 @@ class LocalizationWithMetadata(Localization):
 class VCSLLocalization(LocalizationWithMetadata):
     """Alignment with a VCSL model (only "TN" exists here, as in every call of the reference)."""
 
-    def __init__(self, queries, refs, model_type, similarity_bias=0.0, device=None, **kwargs):
-        super().__init__(queries, refs, device=device)
+    def __init__(self, queries, refs, model_type, similarity_bias=0.0, device=None, ref_codec="Flat", **kwargs):
+        super().__init__(queries, refs, device=device, ref_codec=ref_codec)
         from vsc2022_amd.vcsl.vta import build_vta_model  # late import, as in the reference
 
         self.model = build_vta_model(model_type, **kwargs)
