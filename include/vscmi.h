@@ -293,7 +293,7 @@ int vsc_merge_topk(const float* scores, const int64_t* ids, int64_t nq, int m, i
                    int device);
 
 /* The stream of the entry points that own no handle on `device` (vsc_pair_max, vsc_sort_hits, vsc_score_histogram, vsc_score_pick,
- * vsc_filter_hits, vsc_argsort_scores, vsc_merge_topk, vsc_row_normalize, vsc_tn_forward_sim):
+ * vsc_filter_hits, vsc_argsort_scores, vsc_merge_topk, vsc_row_normalize, vsc_tn_forward_sim, vsc_align_forward_sim):
  * as vsc_index_set_stream. */
 int vsc_set_aux_stream(int device, void* hip_stream, int own);
 
@@ -381,6 +381,42 @@ int vsc_tn_forward_sim(const float* sims, const int64_t* sims_off, const int32_t
 int vsc_tn_similarity(vsc_tn_ctx_t* ctx, int32_t q_vid, int32_t r_vid, float bias, float* out,
                       int64_t cap, int32_t* lq, int32_t* lr);
 
+/* ------------------------------------------------------------- DTW / DP aligners
+ * vcsl.vta.build_vta_model("DTW" / "DP") on the device (vsc2022_amd/vcsl/aligners.py spells both algorithms out choice
+ * by choice; the boxes here are those of its host functions `dtw` / `dp` on the same fp32 matrices, integer for
+ * integer).  One 64-lane workgroup per pair; the similarity tile is vsc_tn_similarity's, bit for bit; the warping-path
+ * costs, path scores and run scores are float64 sums of the host's operands in the host's order, the match / alive
+ * test is `s >= (float)min_sim` in fp32 (as NumPy compares an fp32 matrix with a Python float), the IoU a float64
+ * quotient.  A pair's whole working state lives in LDS: pairs of more than VSC_ALIGN_MAX_CELLS = lq * lr cells are not
+ * attempted (status 1) and are the caller's to align. */
+#define VSC_ALIGN_DTW 1
+#define VSC_ALIGN_DP 2
+#define VSC_ALIGN_MAX_CELLS 9216
+typedef struct vsc_align_params {
+    int32_t method;      /* VSC_ALIGN_DTW / VSC_ALIGN_DP */
+    int32_t discontinue; /* 0..15 */
+    int32_t min_length;  /* >= 0 */
+    int32_t max_path;    /* 0..VSC_TN_MAX_BOXES (DP; DTW ignores it) */
+    double min_sim;
+    double max_iou;
+} vsc_align_params;
+
+/* One localize_all batch through DTW / DP.  Arguments, output layout (out_nbox, out_boxes, out_boxmax), stream and
+ * synchronisation as vsc_tn_localize.  out_status[n_pairs] says who finished a pair:
+ *   0  done here (a pair with an empty video: no boxes)
+ *   1  not attempted: lq * lr > VSC_ALIGN_MAX_CELLS
+ *   2  more than VSC_TN_MAX_BOXES boxes passed the keep filter
+ * out_nbox[p] = 0 whenever out_status[p] != 0.  VSC_ERR_INVALID for a discontinue outside 0..15, a max_path outside
+ * 0..VSC_TN_MAX_BOXES, min_length < 0 or an unknown method. */
+int vsc_tn_align(vsc_tn_ctx_t* ctx, const int32_t* pair_q, const int32_t* pair_r, int64_t n_pairs, int pairs_mem,
+                 const vsc_align_params* params, float bias, int32_t* out_nbox, int32_t* out_boxes, float* out_boxmax,
+                 int32_t* out_status, int out_mem);
+/* The aligners' forward_sim on caller-supplied matrices (host memory, laid out as for vsc_tn_forward_sim); outputs
+ * (host) as above with bias = 0. */
+int vsc_align_forward_sim(const float* sims, const int64_t* sims_off, const int32_t* lq, const int32_t* lr, int64_t n_pairs,
+                          const vsc_align_params* params, int32_t* out_nbox, int32_t* out_boxes, float* out_boxmax,
+                          int32_t* out_status, int device);
+
 /* ---------------------------------------------------------- instrumentation
  * Kernel-time accounting for bench.py: HIP events recorded on the handle's stream around the
  * dominant similarity kernel.  vsc_index_profile(idx, 1) enables it; vsc_index_profile_read
@@ -398,7 +434,8 @@ int vsc_index_profile_read_class(vsc_index_t* idx, int cls, double* ms, int64_t*
                                  int reset);
 /* Process-wide accounting of the entry points that own no index handle, same method (HIP events on the
  * stream the kernels run on): cls 0 = vsc_pair_max (vsc/candidates.py:24-40 on device hits), cls 1 = the
- * Temporal-Network launches of vsc_tn_localize / vsc_tn_forward_sim (vcsl.vta TN.forward_sim).
+ * Temporal-Network launches of vsc_tn_localize / vsc_tn_forward_sim (vcsl.vta TN.forward_sim), cls 2 = the DTW / DP
+ * launches of vsc_tn_align / vsc_align_forward_sim.
  * bytes = algorithmic bytes of the calls (4*dim*(Lq+Lr) per pair + boxes; 12 B per hit
  * + 20 B per pair).  bench.py only. */
 int vsc_aux_profile(int enable);

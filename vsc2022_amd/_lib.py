@@ -34,6 +34,10 @@ CODEC_SQFP16 = 1
 # the codec strings of VideoIndex / faiss.index_factory that exist here
 CODECS = {"Flat": CODEC_FLAT, "SQfp16": CODEC_SQFP16}
 TN_MAX_BOXES = 16
+# DTW / DP aligners on the device (vsc_tn_align, vsc_align_forward_sim)
+ALIGN_DTW = 1
+ALIGN_DP = 2
+ALIGN_MAX_CELLS = 9216  # VSC_ALIGN_MAX_CELLS: lq * lr of the largest pair whose working state fits LDS
 
 # every symbol include/vscmi.h declares
 EXPORTS = (
@@ -44,6 +48,7 @@ EXPORTS = (
     "vsc_index_range_search", "vsc_index_global_topk", "vsc_index_global_topk_seeded", "vsc_index_candidates", "vsc_pair_max", "vsc_sort_hits", "vsc_row_normalize",
     "vsc_score_histogram", "vsc_score_pick", "vsc_filter_hits", "vsc_argsort_scores", "vsc_merge_topk",
     "vsc_tn_create", "vsc_tn_create_codec", "vsc_tn_ref_bytes", "vsc_tn_set_queries", "vsc_tn_destroy", "vsc_tn_localize", "vsc_tn_forward_sim", "vsc_tn_similarity",
+    "vsc_tn_align", "vsc_align_forward_sim",
     "vsc_index_profile", "vsc_index_profile_read", "vsc_index_profile_read_class", "vsc_index_search_stats",
     "vsc_aux_profile", "vsc_aux_profile_read", "vsc_bias_act_bf16", "vsc_gemm_bias_act_bf16", "vsc_pool3x3s2_bias_relu_bf16", "vsc_conv_bias_act_bf16",
     "vsc_vit_attention_bf16", "vsc_layernorm_bf16", "vsc_vit_tokens_bf16", "vsc_vit_cdpool_bf16",
@@ -58,6 +63,17 @@ class TNParams(ctypes.Structure):
         ("min_length", ctypes.c_int32),
         ("min_sim", ctypes.c_float),
         ("max_iou", ctypes.c_float),
+    ]
+
+
+class AlignParams(ctypes.Structure):
+    _fields_ = [
+        ("method", ctypes.c_int32),
+        ("discontinue", ctypes.c_int32),
+        ("min_length", ctypes.c_int32),
+        ("max_path", ctypes.c_int32),
+        ("min_sim", ctypes.c_double),
+        ("max_iou", ctypes.c_double),
     ]
 
 
@@ -189,6 +205,8 @@ def lib():
         L.vsc_tn_localize.argtypes = [vp, vp, vp, i64, i32, ctypes.POINTER(TNParams), f32, vp, vp, vp, i32]
         L.vsc_tn_forward_sim.argtypes = [vp, vp, vp, vp, i64, ctypes.POINTER(TNParams), vp, vp, vp, i32]
         L.vsc_tn_similarity.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, f32, vp, i64, pi32, pi32]
+        L.vsc_tn_align.argtypes = [vp, vp, vp, i64, i32, ctypes.POINTER(AlignParams), f32, vp, vp, vp, vp, i32]
+        L.vsc_align_forward_sim.argtypes = [vp, vp, vp, vp, i64, ctypes.POINTER(AlignParams), vp, vp, vp, vp, i32]
         L.vsc_index_profile.argtypes = [vp, i32]
         L.vsc_index_profile_read.argtypes = [vp, ctypes.POINTER(ctypes.c_double), pi64,
                                              ctypes.POINTER(ctypes.c_double), i32]

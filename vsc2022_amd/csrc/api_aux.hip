@@ -1,5 +1,5 @@
 // C ABI of libvscmi.so, part 4: the entry points that own no index handle (vsc_pair_max, vsc_row_normalize) and the
-// Temporal-Network localisation contexts (vsc_tn_*).
+// Temporal-Network localisation contexts (vsc_tn_*) and the DTW / DP aligners on them (vsc_tn_align, vsc_align_forward_sim).
 #include "api_internal.h"
 
 extern "C" {
@@ -389,6 +389,61 @@ static int tn_run_buckets(TnPairArgs base, const std::vector<int32_t>& lqs, cons
     return VSC_OK;
 }
 
+// ------------------------------------------------------------------------ DTW / DP launches
+
+static int align_check_params(const char* who, const vsc_align_params* p) {
+    if ((p->method != VSC_ALIGN_DTW && p->method != VSC_ALIGN_DP) || p->discontinue < 0 || p->discontinue > 15 || p->min_length < 0 ||
+        p->max_path < 0 || p->max_path > VSC_TN_MAX_BOXES) {
+        set_error("%s: unsupported aligner parameters (method VSC_ALIGN_DTW / VSC_ALIGN_DP, discontinue 0..15, min_length >= 0, "
+                  "max_path 0..%d)", who, VSC_TN_MAX_BOXES);
+        return VSC_ERR_INVALID;
+    }
+    return VSC_OK;
+}
+
+// The pairs of one call in launches by LDS footprint (a workgroup's allocation is the launch's largest: one long pair
+// must not cost the short ones their occupancy).  Every pair is handed to the kernel, which answers the ones it does
+// not run (an empty video; more than VSC_ALIGN_MAX_CELLS cells) with their status alone.
+static int align_run_buckets(AlignArgs base, const std::vector<int32_t>& lqs, const std::vector<int32_t>& lrs, DevBuf& d_work,
+                             hipStream_t stream) {
+    const int64_t n_pairs = (int64_t)lqs.size();
+    const bool fused = base.sims_in == nullptr;
+    constexpr size_t kBucketMax[3] = {24 * 1024, 64 * 1024, ALIGN_LDS_MAX};
+    struct Bucket { std::vector<int32_t> work; size_t lds = 0; double bytes = 0.0; } buckets[3];
+    for (int64_t p = 0; p < n_pairs; ++p) {
+        const int64_t lq = lqs[(size_t)p], lr = lrs[(size_t)p];
+        size_t need = 0;
+        double bytes = 8.0 + 20.0 * VSC_TN_MAX_BOXES;
+        if (lq > 0 && lr > 0 && lq * lr <= VSC_ALIGN_MAX_CELLS) {
+            need = align_layout(base.prm.method, (int)lq, (int)lr, fused).total;
+            // algorithmic bytes: the descriptor rows of the pair once (fused) or its matrix (forward_sim), + the boxes out
+            bytes += fused ? base.dpad * (4.0 * lq + (base.rfeat_h ? 2.0 : 4.0) * lr) : 4.0 * lq * lr;
+        }
+        const int b = need <= kBucketMax[0] ? 0 : (need <= kBucketMax[1] ? 1 : 2);
+        buckets[b].work.push_back((int32_t)p);
+        buckets[b].lds = std::max(buckets[b].lds, need);
+        buckets[b].bytes += bytes;
+    }
+    VSC_TRY(d_work.reserve((size_t)std::max<int64_t>(n_pairs, 1) * 4));
+    int64_t woff = 0;
+    AuxTimer tm;
+    tm.begin(2, stream);
+    for (Bucket& B : buckets) {
+        if (B.work.empty()) continue;
+        int32_t* dwork = d_work.as<int32_t>() + woff;
+        VSC_HIP(hipMemcpyAsync(dwork, B.work.data(), B.work.size() * 4, hipMemcpyHostToDevice, stream));
+        AlignArgs a = base;
+        a.work = dwork;
+        a.n_work = (int)B.work.size();
+        VSC_TRY(launch_align_pairs(a, B.lds, stream));
+        tm.end(B.bytes, stream);
+        woff += (int64_t)B.work.size();
+    }
+    VSC_HIP(hipStreamSynchronize(stream));  // (the host work lists are read by the copies above)
+    tm.collect();
+    return VSC_OK;
+}
+
 // ------------------------------------------------------------------------ TN context
 
 struct vsc_tn_ctx {
@@ -401,7 +456,7 @@ struct vsc_tn_ctx {
     int64_t n_qvid = 0, n_rvid = 0;
     std::vector<int64_t> q_off, r_off;  // host copies
     DevBuf qfeat, rfeat, rfeat_h, d_qoff, d_roff;
-    DevBuf d_pq, d_pr, d_work, d_nbox, d_boxes, d_bmax, slab, sims;
+    DevBuf d_pq, d_pr, d_work, d_nbox, d_boxes, d_bmax, d_status, slab, sims;
     Workspace ws;
     hipStream_t stream = nullptr;      // own_stream, or the caller's (vsc_tn_set_stream)
     hipStream_t own_stream = nullptr;
@@ -587,10 +642,44 @@ int vsc_tn_destroy(vsc_tn_ctx_t* c) {
     else (void)hipDeviceSynchronize();
     c->qfeat.release(); c->rfeat.release(); c->rfeat_h.release(); c->d_qoff.release(); c->d_roff.release();
     c->d_pq.release(); c->d_pr.release(); c->d_work.release(); c->d_nbox.release();
-    c->d_boxes.release(); c->d_bmax.release(); c->slab.release(); c->sims.release();
+    c->d_boxes.release(); c->d_bmax.release(); c->d_status.release(); c->slab.release(); c->sims.release();
     c->ws.release();
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
+    return VSC_OK;
+}
+
+// The pair list of one batch on both sides -- the context's device copy (d_pq / d_pr) for the kernel, the frame counts
+// of every pair on the host for bucketing -- with the ordinals checked against the context's videos.
+static int tn_pair_shapes(vsc_tn_ctx* c, const char* who, const int32_t* pair_q, const int32_t* pair_r, int64_t n_pairs, int pairs_mem,
+                          std::vector<int32_t>& lqs, std::vector<int32_t>& lrs) {
+    // pair lists on both sides: host for bucketing, device for the kernel
+    std::vector<int32_t> hq((size_t)n_pairs), hr((size_t)n_pairs);
+    VSC_TRY(c->d_pq.reserve((size_t)n_pairs * 4));
+    VSC_TRY(c->d_pr.reserve((size_t)n_pairs * 4));
+    if (pairs_mem == VSC_MEM_HOST) {
+        memcpy(hq.data(), pair_q, (size_t)n_pairs * 4);
+        memcpy(hr.data(), pair_r, (size_t)n_pairs * 4);
+        VSC_HIP(hipMemcpyAsync(c->d_pq.p, pair_q, (size_t)n_pairs * 4, hipMemcpyHostToDevice, c->stream));
+        VSC_HIP(hipMemcpyAsync(c->d_pr.p, pair_r, (size_t)n_pairs * 4, hipMemcpyHostToDevice, c->stream));
+    } else {
+        VSC_HIP(hipMemcpyAsync(hq.data(), pair_q, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, c->stream));
+        VSC_HIP(hipMemcpyAsync(hr.data(), pair_r, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, c->stream));
+        VSC_HIP(hipMemcpyAsync(c->d_pq.p, pair_q, (size_t)n_pairs * 4, hipMemcpyDeviceToDevice, c->stream));
+        VSC_HIP(hipMemcpyAsync(c->d_pr.p, pair_r, (size_t)n_pairs * 4, hipMemcpyDeviceToDevice, c->stream));
+    }
+    VSC_HIP(hipStreamSynchronize(c->stream));
+    lqs.resize((size_t)n_pairs);
+    lrs.resize((size_t)n_pairs);
+    for (int64_t p = 0; p < n_pairs; ++p) {
+        const int32_t qv = hq[(size_t)p], rv = hr[(size_t)p];
+        if (qv < 0 || qv >= c->n_qvid || rv < 0 || rv >= c->n_rvid) {
+            set_error("%s: pair %lld has video ordinal out of range", who, (long long)p);
+            return VSC_ERR_INVALID;
+        }
+        lqs[(size_t)p] = (int32_t)std::min<int64_t>(c->q_off[qv + 1] - c->q_off[qv], 0x7fffffff);
+        lrs[(size_t)p] = (int32_t)std::min<int64_t>(c->r_off[rv + 1] - c->r_off[rv], 0x7fffffff);
+    }
     return VSC_OK;
 }
 
@@ -611,32 +700,8 @@ int vsc_tn_localize(vsc_tn_ctx_t* c, const int32_t* pair_q, const int32_t* pair_
         return VSC_ERR_INVALID;
     }
     VSC_HIP(hipSetDevice(c->device));
-    // pair lists on both sides: host for bucketing, device for the kernel
-    std::vector<int32_t> hq((size_t)n_pairs), hr((size_t)n_pairs);
-    VSC_TRY(c->d_pq.reserve((size_t)n_pairs * 4));
-    VSC_TRY(c->d_pr.reserve((size_t)n_pairs * 4));
-    if (pairs_mem == VSC_MEM_HOST) {
-        memcpy(hq.data(), pair_q, (size_t)n_pairs * 4);
-        memcpy(hr.data(), pair_r, (size_t)n_pairs * 4);
-        VSC_HIP(hipMemcpyAsync(c->d_pq.p, pair_q, (size_t)n_pairs * 4, hipMemcpyHostToDevice, c->stream));
-        VSC_HIP(hipMemcpyAsync(c->d_pr.p, pair_r, (size_t)n_pairs * 4, hipMemcpyHostToDevice, c->stream));
-    } else {
-        VSC_HIP(hipMemcpyAsync(hq.data(), pair_q, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, c->stream));
-        VSC_HIP(hipMemcpyAsync(hr.data(), pair_r, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, c->stream));
-        VSC_HIP(hipMemcpyAsync(c->d_pq.p, pair_q, (size_t)n_pairs * 4, hipMemcpyDeviceToDevice, c->stream));
-        VSC_HIP(hipMemcpyAsync(c->d_pr.p, pair_r, (size_t)n_pairs * 4, hipMemcpyDeviceToDevice, c->stream));
-    }
-    VSC_HIP(hipStreamSynchronize(c->stream));
-    std::vector<int32_t> lqs((size_t)n_pairs), lrs((size_t)n_pairs);
-    for (int64_t p = 0; p < n_pairs; ++p) {
-        const int32_t qv = hq[(size_t)p], rv = hr[(size_t)p];
-        if (qv < 0 || qv >= c->n_qvid || rv < 0 || rv >= c->n_rvid) {
-            set_error("vsc_tn_localize: pair %lld has video ordinal out of range", (long long)p);
-            return VSC_ERR_INVALID;
-        }
-        lqs[(size_t)p] = (int32_t)std::min<int64_t>(c->q_off[qv + 1] - c->q_off[qv], 0x7fffffff);
-        lrs[(size_t)p] = (int32_t)std::min<int64_t>(c->r_off[rv + 1] - c->r_off[rv], 0x7fffffff);
-    }
+    std::vector<int32_t> lqs, lrs;
+    VSC_TRY(tn_pair_shapes(c, "vsc_tn_localize", pair_q, pair_r, n_pairs, pairs_mem, lqs, lrs));
     int32_t* d_nbox = out_nbox;
     int32_t* d_boxes = out_boxes;
     float* d_bmax = out_boxmax;
@@ -726,6 +791,115 @@ int vsc_tn_forward_sim(const float* sims, const int64_t* sims_off, const int32_t
     VSC_HIP(hipMemcpyAsync(out_nbox, ws.out[0].p, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, c->stream));
     VSC_HIP(hipMemcpyAsync(out_boxes, ws.out[1].p, (size_t)n_pairs * VSC_TN_MAX_BOXES * 16, hipMemcpyDeviceToHost, c->stream));
     VSC_HIP(hipMemcpyAsync(out_boxmax, ws.out[2].p, (size_t)n_pairs * VSC_TN_MAX_BOXES * 4, hipMemcpyDeviceToHost, c->stream));
+    VSC_HIP(hipStreamSynchronize(c->stream));
+    return VSC_OK;
+}
+
+int vsc_tn_align(vsc_tn_ctx_t* c, const int32_t* pair_q, const int32_t* pair_r, int64_t n_pairs, int pairs_mem,
+                 const vsc_align_params* params, float bias, int32_t* out_nbox, int32_t* out_boxes, float* out_boxmax,
+                 int32_t* out_status, int out_mem) {
+    if (!c || n_pairs < 0 || !params ||
+        (n_pairs > 0 && (!pair_q || !pair_r || !out_nbox || !out_boxes || !out_boxmax || !out_status))) {
+        set_error("vsc_tn_align: invalid argument");
+        return VSC_ERR_INVALID;
+    }
+    VSC_TRY(align_check_params("vsc_tn_align", params));
+    if (n_pairs == 0) return VSC_OK;
+    VSC_HIP(hipSetDevice(c->device));
+    std::vector<int32_t> lqs, lrs;
+    VSC_TRY(tn_pair_shapes(c, "vsc_tn_align", pair_q, pair_r, n_pairs, pairs_mem, lqs, lrs));
+    AlignArgs base;
+    memset(&base, 0, sizeof(base));
+    base.out_nbox = out_nbox;
+    base.out_boxes = out_boxes;
+    base.out_boxmax = out_boxmax;
+    base.out_status = out_status;
+    if (out_mem == VSC_MEM_HOST) {
+        VSC_TRY(c->d_nbox.reserve((size_t)n_pairs * 4));
+        VSC_TRY(c->d_boxes.reserve((size_t)n_pairs * VSC_TN_MAX_BOXES * 16));
+        VSC_TRY(c->d_bmax.reserve((size_t)n_pairs * VSC_TN_MAX_BOXES * 4));
+        VSC_TRY(c->d_status.reserve((size_t)n_pairs * 4));
+        base.out_nbox = c->d_nbox.as<int32_t>();
+        base.out_boxes = c->d_boxes.as<int32_t>();
+        base.out_boxmax = c->d_bmax.as<float>();
+        base.out_status = c->d_status.as<int32_t>();
+    }
+    base.qfeat = c->qfeat.as<float>();
+    base.rfeat = c->rfeat.as<float>();
+    base.rfeat_h = c->rfeat_h.as<_Float16>();  // (nullptr in a Flat context)
+    base.q_off = c->d_qoff.as<int64_t>();
+    base.r_off = c->d_roff.as<int64_t>();
+    base.dpad = c->dpad;
+    base.pair_q = c->d_pq.as<int32_t>();
+    base.pair_r = c->d_pr.as<int32_t>();
+    base.prm = *params;
+    base.bias = bias;
+    VSC_TRY(align_run_buckets(base, lqs, lrs, c->d_work, c->stream));
+    if (out_mem == VSC_MEM_HOST) {
+        VSC_HIP(hipMemcpyAsync(out_nbox, base.out_nbox, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, c->stream));
+        VSC_HIP(hipMemcpyAsync(out_boxes, base.out_boxes, (size_t)n_pairs * VSC_TN_MAX_BOXES * 16, hipMemcpyDeviceToHost, c->stream));
+        VSC_HIP(hipMemcpyAsync(out_boxmax, base.out_boxmax, (size_t)n_pairs * VSC_TN_MAX_BOXES * 4, hipMemcpyDeviceToHost, c->stream));
+        VSC_HIP(hipMemcpyAsync(out_status, base.out_status, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    VSC_HIP(hipStreamSynchronize(c->stream));
+    return VSC_OK;
+}
+
+int vsc_align_forward_sim(const float* sims, const int64_t* sims_off, const int32_t* lq, const int32_t* lr, int64_t n_pairs,
+                          const vsc_align_params* params, int32_t* out_nbox, int32_t* out_boxes, float* out_boxmax,
+                          int32_t* out_status, int device) {
+    if (n_pairs < 0 || !params ||
+        (n_pairs > 0 && (!sims || !sims_off || !lq || !lr || !out_nbox || !out_boxes || !out_boxmax || !out_status))) {
+        set_error("vsc_align_forward_sim: invalid argument");
+        return VSC_ERR_INVALID;
+    }
+    VSC_TRY(align_check_params("vsc_align_forward_sim", params));
+    if (n_pairs == 0) return VSC_OK;
+    for (int64_t p = 0; p < n_pairs; ++p)
+        if (lq[p] < 0 || lr[p] < 0 || sims_off[p + 1] - sims_off[p] < (int64_t)lq[p] * lr[p]) {
+            set_error("vsc_align_forward_sim: pair %lld has a negative shape or a matrix shorter than lq * lr", (long long)p);
+            return VSC_ERR_INVALID;
+        }
+    VSC_TRY(check_device(device));
+    VSC_HIP(hipSetDevice(device));
+    DeviceCtx* c = device_ctx(device);
+    if (!c) {
+        set_error("vsc_align_forward_sim: cannot create device context");
+        return VSC_ERR_HIP;
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    Workspace& ws = c->ws;
+    const int64_t total = sims_off[n_pairs];
+    VSC_TRY(ws.mat.reserve((size_t)std::max<int64_t>(total, 1) * 4));
+    VSC_TRY(ws.sort.w0.reserve((size_t)(n_pairs + 1) * 8));
+    VSC_TRY(ws.sort.w2.reserve((size_t)n_pairs * 4));
+    VSC_TRY(ws.sort.w3.reserve((size_t)n_pairs * 4));
+    VSC_TRY(ws.out[0].reserve((size_t)n_pairs * 4));
+    VSC_TRY(ws.out[1].reserve((size_t)n_pairs * VSC_TN_MAX_BOXES * 16));
+    VSC_TRY(ws.out[2].reserve((size_t)n_pairs * VSC_TN_MAX_BOXES * 4));
+    VSC_TRY(ws.out[3].reserve((size_t)n_pairs * 4));
+    if (total > 0) VSC_HIP(hipMemcpyAsync(ws.mat.p, sims, (size_t)total * 4, hipMemcpyHostToDevice, c->stream));
+    VSC_HIP(hipMemcpyAsync(ws.sort.w0.p, sims_off, (size_t)(n_pairs + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    VSC_HIP(hipMemcpyAsync(ws.sort.w2.p, lq, (size_t)n_pairs * 4, hipMemcpyHostToDevice, c->stream));
+    VSC_HIP(hipMemcpyAsync(ws.sort.w3.p, lr, (size_t)n_pairs * 4, hipMemcpyHostToDevice, c->stream));
+    AlignArgs base;
+    memset(&base, 0, sizeof(base));
+    base.prm = *params;
+    base.bias = 0.0f;
+    base.out_nbox = ws.out[0].as<int32_t>();
+    base.out_boxes = ws.out[1].as<int32_t>();
+    base.out_boxmax = ws.out[2].as<float>();
+    base.out_status = ws.out[3].as<int32_t>();
+    base.sims_in = ws.mat.as<float>();
+    base.sims_off = ws.sort.w0.as<int64_t>();
+    base.sims_lq = ws.sort.w2.as<int32_t>();
+    base.sims_lr = ws.sort.w3.as<int32_t>();
+    std::vector<int32_t> lqs(lq, lq + n_pairs), lrs(lr, lr + n_pairs);
+    VSC_TRY(align_run_buckets(base, lqs, lrs, ws.maps0, c->stream));
+    VSC_HIP(hipMemcpyAsync(out_nbox, ws.out[0].p, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, c->stream));
+    VSC_HIP(hipMemcpyAsync(out_boxes, ws.out[1].p, (size_t)n_pairs * VSC_TN_MAX_BOXES * 16, hipMemcpyDeviceToHost, c->stream));
+    VSC_HIP(hipMemcpyAsync(out_boxmax, ws.out[2].p, (size_t)n_pairs * VSC_TN_MAX_BOXES * 4, hipMemcpyDeviceToHost, c->stream));
+    VSC_HIP(hipMemcpyAsync(out_status, ws.out[3].p, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, c->stream));
     VSC_HIP(hipStreamSynchronize(c->stream));
     return VSC_OK;
 }

@@ -189,12 +189,13 @@ int prof_end(vsc_index* idx, hipEvent_t stop, double work, int cls = 0);  // `wo
 int prof_collect(vsc_index* idx);                                         // call after a stream sync
 
 // Process-wide kernel-time accounting of the entry points that own no index handle (HIP events on the stream
-// the kernels run on; read after the call's own stream sync): 0 = vsc_pair_max, 1 = Temporal-Network launches.
+// the kernels run on; read after the call's own stream sync): 0 = vsc_pair_max, 1 = Temporal-Network launches,
+// 2 = DTW / DP launches.
 struct AuxProf {
     bool on = false;
     std::mutex mu;
-    double ms[2] = {}, bytes[2] = {};
-    int64_t n[2] = {};
+    double ms[3] = {}, bytes[3] = {};
+    int64_t n[3] = {};
 };
 extern AuxProf g_aux;
 struct AuxTimer {

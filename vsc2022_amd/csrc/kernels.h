@@ -160,6 +160,59 @@ struct TnSimsArgs {
     const _Float16* rfeat_h;  // as in TnPairArgs
 };
 
+// DTW / DP aligners (align.hip): one candidate pair per single-wavefront workgroup, as tn_pair_kernel; the fields the
+// similarity tile reads (tn_sims.h) carry TnPairArgs' names
+struct AlignArgs {
+    const float* qfeat; const float* rfeat; const int64_t* q_off; const int64_t* r_off; int dpad;
+    const int32_t* pair_q; const int32_t* pair_r; const int32_t* work; int n_work; vsc_align_params prm;
+    float bias;
+    int32_t* out_nbox; int32_t* out_boxes; float* out_boxmax; int32_t* out_status;
+    // forward_sim mode (sims_in != nullptr): precomputed matrices, pair p at sims_in + sims_off[p]
+    const float* sims_in; const int64_t* sims_off; const int32_t* sims_lq; const int32_t* sims_lr;
+    const _Float16* rfeat_h;  // as in TnPairArgs
+};
+// The working state of one pair, all of it in LDS: byte offsets into the workgroup's dynamic array and their sum.  The
+// kernel carves by the pair's own shape; a launch asks for the largest `total` among its pairs.
+//   both: tile   the similarity matrix, fp32 [lq][lr] (not in forward_sim mode: the caller's matrix is read in place)
+//         kept   the boxes that passed the keep filter, int [VSC_TN_MAX_BOXES][4]
+//   DTW:  f64    three rolling anti-diagonals of D, double [min(lq, lr) + 1] each
+//         runs   score (double) and box (4 x uint16) of every run of the warping path: at most (lq + lr) / 2 runs (a
+//                path of lq + lr - 1 cells at most, a non-matching cell between two runs at least)
+//         bytes  the traceback rule of every cell, decided when the cell is filled (0 diagonal, 1 up, 2 left: [lq][lr]),
+//                then the lq + lr steps of the path at most
+//   DP:   f64    S, double [lq][lr]
+//         runs   the boxes in extraction order, int [VSC_TN_MAX_BOXES][4]
+//         u16    the predecessor step of every cell, (a << 8) | b, 0 = none
+//         bytes  dead-row and dead-column flags, [lq] + [lr]
+struct AlignLayout { size_t f64, runs, tile, kept, u16, bytes, total; };
+__host__ __device__ inline AlignLayout align_layout(int method, int lq, int lr, bool tile_in_lds) {
+    const size_t cells = (size_t)lq * lr, edge = (size_t)lq + lr;
+    const bool dtw = method == VSC_ALIGN_DTW;
+    AlignLayout L;
+    size_t off = 0;
+    L.f64 = off;
+    off += dtw ? 3 * ((size_t)(lq < lr ? lq : lr) + 1) * 8 : cells * 8;
+    L.runs = off;
+    off += dtw ? (edge / 2 + 1) * 16 : (size_t)VSC_TN_MAX_BOXES * 16;
+    L.tile = off;
+    off += tile_in_lds ? cells * 4 : 0;
+    L.kept = off;
+    off += (size_t)VSC_TN_MAX_BOXES * 16;
+    L.u16 = off;
+    off += dtw ? 0 : cells * 2;
+    L.bytes = off;
+    off += dtw ? cells + edge : edge;
+    L.total = (off + 15) & ~(size_t)15;
+    return L;
+}
+// The launches' LDS budget.  Every pair of at most VSC_ALIGN_MAX_CELLS cells fits: lq + lr <= cells + 1 and
+// min(lq, lr) <= sqrt(cells) bound the layout above by 14 B per cell + 1 B per edge frame (DP), or 5 B per cell + 9 B per
+// edge frame (DTW), + 3 KiB of fixed parts
+constexpr size_t ALIGN_LDS_MAX = 150 * 1024;
+static_assert(14 * (size_t)VSC_ALIGN_MAX_CELLS + (VSC_ALIGN_MAX_CELLS + 1) + 3072 <= ALIGN_LDS_MAX, "DP state of the largest pair");
+static_assert(5 * (size_t)VSC_ALIGN_MAX_CELLS + 9 * (VSC_ALIGN_MAX_CELLS + 1) + 3072 <= ALIGN_LDS_MAX, "DTW state of the largest pair");
+static_assert(VSC_ALIGN_MAX_CELLS < 32768, "frame indices are kept in 16 bits");
+
 int launch_sim_thresh(const SimThreshArgs&, hipStream_t);
 int launch_sim_f16(const SimF16Args&, hipStream_t);
 int sim_f16_grid(int tq, int tr);
@@ -214,6 +267,7 @@ int launch_row_normalize(const float*, int64_t, int, float*, hipStream_t);
 size_t tn_state_bytes_host(int, int, int, int idx_bytes = 2);
 int launch_tn_pairs(const TnPairArgs&, size_t, hipStream_t);
 int launch_tn_sims(const TnSimsArgs&, hipStream_t);
+int launch_align_pairs(const AlignArgs&, size_t, hipStream_t);
 // SQfp16 codec (codec_f16.hip)
 int launch_encode_rows(const void*, bool, int64_t, int, _Float16*, float*, int64_t, int64_t, int, bool, int*, hipStream_t);
 int launch_decode_rows(const _Float16*, int, bool, int64_t, int64_t, int64_t, float*, int, bool, hipStream_t);

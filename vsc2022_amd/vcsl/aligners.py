@@ -4,7 +4,8 @@ The reference passes any `model_type` through to VCSL (vsc/baseline/localization
 but "TN" (vsc/baseline/sscd_baseline.py:121,131; vsc/baseline/dns_baseline.py:202); VCSL's own DTW / DP are CPU code
 (numba) that takes the frame x frame similarity matrix of a pair.  They run the same way here: the matrices come from the
 GPU (`VCSLLocalization.similarity`, libvscmi), the alignment below runs on the host inside `forward_sim`, box scores go
-through the localiser's `score()` hook -- the reference's own route, off the hot path.
+through the localiser's `score()` hook -- the reference's own route.  DTW and DP also exist as
+HIP kernels (csrc/align.hip), opt-in with `on_device=True`: the functions below are their contract, box for box.
 
 PARITY UNPINNED, like TN: the VCSL source is not part of the reference checkout (dangling symlink, .gitmodules:1-3), so
 these are restatements of the published algorithms (He et al., CVPR 2022, section 5.1: "DTW" = dynamic time warping over
@@ -235,29 +236,92 @@ def hv(sims: np.ndarray, discontinue: int = 3, min_sim: float = 0.2, min_length:
 
 class _HostAligner:
     """`forward_sim([(name, sims), ...]) -> [(name, boxes), ...]` in input order, names echoed (the contract of
-    vsc/baseline/localization.py:58-66).  `concurrency` (a process-pool size in VCSL) is accepted and ignored."""
+    vsc/baseline/localization.py:58-66).  `concurrency` (a process-pool size in VCSL) is accepted and ignored.
+
+    `on_device=True` (DTW and DP) aligns on the GPU instead (libvscmi vsc_align_forward_sim, one pair per workgroup;
+    `device`: its ordinal, None = the process's default): the matrices are taken as float32 and the result is the host
+    function's on those, box for box -- a pair the kernel does not finish (more than `_lib.ALIGN_MAX_CELLS` cells, more
+    than `_lib.TN_MAX_BOXES` boxes) is aligned by the host function.  The parameters are then kept as int / float, and
+    the ones the kernel has no room for (discontinue beyond 15, max_path beyond 16, a negative min_length) are refused
+    here.  No device is touched before the first `forward_sim`.  `VCSLLocalization*(..., on_device=True)` passes the flag
+    through and then aligns a whole candidate batch without a matrix leaving the GPU (vsc_tn_align)."""
 
     _fn = None
     _defaults: dict = {}
+    _method = None  # _lib.ALIGN_* of the device form; None: host only
 
-    def __init__(self, concurrency: int = 1, **config):
+    def __init__(self, concurrency: int = 1, on_device: bool = False, device=None, **config):
         unknown = set(config) - set(self._defaults)
         if unknown:
             raise TypeError(f"unexpected {type(self).__name__} arguments: {sorted(unknown)}")
         self.config = dict(self._defaults, **config)
+        self.on_device = bool(on_device)
+        self.device = device
+        if self.on_device:
+            if self._method is None:
+                raise NotImplementedError(f"{type(self).__name__} runs on the host only; 'DTW' and 'DP' have device forms")
+            from vsc2022_amd import _lib
+
+            cfg = {k: (float(v) if k in ("min_sim", "max_iou") else int(v)) for k, v in self.config.items()}
+            if not 0 <= cfg["discontinue"] <= 15:
+                raise ValueError(f"on_device: discontinue must be in 0..15, got {cfg['discontinue']}")
+            if cfg["min_length"] < 0:
+                raise ValueError(f"on_device: min_length must be >= 0, got {cfg['min_length']}")
+            if not 0 <= cfg.get("max_path", 0) <= _lib.TN_MAX_BOXES:
+                raise ValueError(f"on_device: max_path must be in 0..{_lib.TN_MAX_BOXES}, got {cfg['max_path']}")
+            self.config = cfg
+            self.params = _lib.AlignParams(self._method, cfg["discontinue"], cfg["min_length"], cfg.get("max_path", 0),
+                                           cfg["min_sim"], cfg["max_iou"])
 
     def forward_sim(self, data: Sequence[Tuple[str, np.ndarray]]) -> List[Tuple[str, List[List[int]]]]:
+        if self.on_device:
+            return self._forward_sim_device(data)
         return [(name, type(self)._fn(np.asarray(sims), **self.config)) for name, sims in data]
+
+    def _forward_sim_device(self, data):
+        import ctypes
+
+        from vsc2022_amd import _lib
+        from vsc2022_amd.vcsl.vta import unpack_boxes
+
+        names = [name for name, _ in data]
+        mats = [_lib.f32c(sim) for _, sim in data]
+        n = len(mats)
+        if n == 0:
+            return []
+        for m in mats:
+            if m.ndim != 2:
+                raise ValueError("forward_sim expects 2-D similarity matrices")
+        lq = np.array([m.shape[0] for m in mats], dtype=np.int32)
+        lr = np.array([m.shape[1] for m in mats], dtype=np.int32)
+        off = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(lq.astype(np.int64) * lr, out=off[1:])
+        flat = np.concatenate([m.reshape(-1) for m in mats]) if off[-1] else np.zeros(1, np.float32)
+        nbox = np.zeros(n, dtype=np.int32)
+        boxes = np.zeros((n, _lib.TN_MAX_BOXES, 4), dtype=np.int32)
+        bmax = np.zeros((n, _lib.TN_MAX_BOXES), dtype=np.float32)
+        status = np.zeros(n, dtype=np.int32)
+        device = _lib.default_device() if self.device is None else self.device
+        _lib.check(_lib.lib().vsc_align_forward_sim(
+            flat.ctypes.data, off.ctypes.data, lq.ctypes.data, lr.ctypes.data, n, ctypes.byref(self.params),
+            nbox.ctypes.data, boxes.ctypes.data, bmax.ctypes.data, status.ctypes.data, device))
+        self.last_status = status  # per pair: 0 aligned on the device, 1 / 2 by the host function (include/vscmi.h)
+        out = unpack_boxes(nbox, boxes)
+        for p in np.nonzero(status)[0]:
+            out[p] = type(self)._fn(mats[p], **self.config)
+        return list(zip(names, out))
 
 
 class DTW(_HostAligner):
     _fn = staticmethod(dtw)
     _defaults = dict(discontinue=3, min_sim=0.2, min_length=5, max_iou=0.3)
+    _method = 1  # _lib.ALIGN_DTW
 
 
 class DP(_HostAligner):
     _fn = staticmethod(dp)
     _defaults = dict(discontinue=3, min_sim=0.2, min_length=5, max_iou=0.3, max_path=10)
+    _method = 2  # _lib.ALIGN_DP
 
 
 class HV(_HostAligner):

@@ -4,7 +4,8 @@ tests/test_localization.py:17): `build_vta_model(model_type, **kwargs)` returnin
 
 "TN" -- the only model the reference ever requests (sscd_baseline.py:121,131; dns_baseline.py:202) -- runs on the GPU
 (libvscmi vsc_tn_forward_sim, one candidate pair per workgroup).  "DTW", "DP" and "HV" (vsc2022_amd/vcsl/aligners.py) are
-host code over the similarity matrices, as VCSL's own are: the reference's route, off the hot path.  "SPD" is a trained
+host code over the similarity matrices, as VCSL's own are: the reference's route.  "DTW" and "DP" also run on the GPU,
+opt-in with `on_device=True` (libvscmi vsc_align_forward_sim / vsc_tn_align), with the host functions' boxes.  "SPD" is a trained
 detector network whose weights ship with VCSL only: not buildable here (aligners.py, module docstring).  The third-party
 VCSL source is not part of the reference checkout; see DESIGN.md ("TN: parity unpinned" -- the same holds for these).
 """
@@ -90,7 +91,7 @@ def build_vta_model(method="TN", concurrency: int = 1, **config):
     if method in _REGISTRY:
         return _REGISTRY[method](concurrency=concurrency, **config)
     raise NotImplementedError(
-        f"alignment model {method!r}: 'TN' (GPU), 'DTW', 'DP' and 'HV' (host) ship with this package; VCSL's 'SPD' is a "
+        f"alignment model {method!r}: 'TN' (GPU), 'DTW', 'DP' (host or GPU), 'HV' (host) ship with this package; VCSL's 'SPD' is a "
         "TRAINED detector network over the similarity matrix -- its weights ship with VCSL, which is not part of the "
         "reference checkout, and the reference never requests it; register a model that has them with "
         "vsc2022_amd.vcsl.vta.register_vta_model"

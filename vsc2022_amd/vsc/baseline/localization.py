@@ -8,10 +8,11 @@ Class surface of the reference module (`Localization`, `LocalizationWithMetadata
 How it runs here: the constructor uploads both descriptor sets once into a libvscmi TN context
 (HBM resident).  `localize_all` then sends only the (query ordinal, reference ordinal) list of the
 batch; one workgroup per pair computes the frame x frame similarity on the matrix cores, runs the
-Temporal-Network alignment and scores the boxes, and the host merely converts box corners to
-timestamps.  A subclass that overrides `score` (or `similarity`) in a way the fused kernel cannot
-know is still honoured: it falls back to the reference's route -- similarity matrices on the host,
-`self.model.forward_sim(...)`, `self.score(...)` per box.
+Temporal-Network alignment (or, with `on_device=True`, the DTW / DP one) and scores the boxes, and
+the host merely converts box corners to timestamps.  A subclass that overrides `score` (or
+`similarity`) in a way the fused kernel cannot know is still honoured: it falls back to the
+reference's route -- similarity matrices on the host, `self.model.forward_sim(...)`,
+`self.score(...)` per box.
 """
 import abc
 import ctypes
@@ -99,7 +100,8 @@ class LocalizationWithMetadata(Localization):
 
 
 class VCSLLocalization(LocalizationWithMetadata):
-    """Alignment with a VCSL model (only "TN" exists here, as in every call of the reference)."""
+    """Alignment with a VCSL model: "TN" (GPU; the only one the reference ever asks for), "DTW" / "DP" (host, or GPU with
+    `on_device=True`), "HV" (host) -- vcsl.vta.build_vta_model."""
 
     def __init__(self, queries, refs, model_type, similarity_bias=0.0, device=None, ref_codec="Flat", **kwargs):
         super().__init__(queries, refs, device=device, ref_codec=ref_codec)
@@ -141,6 +143,45 @@ class VCSLLocalization(LocalizationWithMetadata):
                      query_start=query.get_timestamps(x1)[0], query_end=query.get_timestamps(x2)[1],
                      ref_start=ref.get_timestamps(y1)[0], ref_end=ref.get_timestamps(y2)[1])
 
+    def _can_fuse_align(self) -> bool:
+        """An on-device DTW / DP model (`on_device=True`) with the stock `score` / `similarity`: the conditions of
+        `_can_fuse`, for the aligner kernels (libvscmi vsc_tn_align)."""
+        from vsc2022_amd.vcsl import aligners
+
+        stock_scores = (VCSLLocalization.score, VCSLLocalizationMaxSim.score, VCSLLocalizationCandidateScore.score)
+        return (type(self.model) in (aligners.DTW, aligners.DP) and self.model.on_device
+                and type(self).score in stock_scores and type(self).similarity is VCSLLocalization.similarity)
+
+    def _aligned_boxes(self, candidates: Sequence[CandidatePair]):
+        n = len(candidates)
+        pair_q = np.fromiter((self._q_ordinal[c.query_id] for c in candidates), dtype=np.int32, count=n)
+        pair_r = np.fromiter((self._r_ordinal[c.ref_id] for c in candidates), dtype=np.int32, count=n)
+        n_boxes = np.zeros(n, dtype=np.int32)
+        boxes = np.zeros((n, _lib.TN_MAX_BOXES, 4), dtype=np.int32)
+        box_max = np.zeros((n, _lib.TN_MAX_BOXES), dtype=np.float32)
+        status = np.zeros(n, dtype=np.int32)
+        _lib.check(_lib.lib().vsc_tn_align(
+            self._ctx, pair_q.ctypes.data, pair_r.ctypes.data, n, _lib.MEM_HOST, ctypes.byref(self.model.params),
+            float(self.similarity_bias), n_boxes.ctypes.data, boxes.ctypes.data, box_max.ctypes.data, status.ctypes.data,
+            _lib.MEM_HOST))
+        return n_boxes, boxes, box_max, status
+
+    def _reference_route(self, candidates: Sequence[CandidatePair]) -> List[List[Match]]:
+        """The reference's route: matrices on the host, any model, any score hook.  One list of matches per candidate."""
+        named = [(f"{c.query_id}-{c.ref_id}", self.similarity(c)) for c in candidates]
+        results = self.model.forward_sim(named)
+        assert len(results) == len(candidates)
+        out: List[List[Match]] = []
+        for candidate, (key, sim), (name, pair_boxes) in zip(candidates, named, results):
+            assert key == name
+            matches = []
+            for box in pair_boxes:
+                box = tuple(int(v) for v in box)
+                match = self._to_match(candidate, box)
+                matches.append(match._replace(score=self.score(candidate, match, box, sim)))
+            out.append(matches)
+        return out
+
     def localize_all(self, candidates: List[CandidatePair]) -> List[Match]:
         candidates = list(candidates)
         if not candidates:
@@ -153,16 +194,22 @@ class VCSLLocalization(LocalizationWithMetadata):
                     match = self._to_match(candidate, [int(v) for v in boxes[k, b]])
                     matches.append(match._replace(score=self._fused_score(candidate, box_max[k, b])))
             return matches
-        # the reference's route: matrices on the host, any model, any score hook
-        named = [(f"{c.query_id}-{c.ref_id}", self.similarity(c)) for c in candidates]
-        results = self.model.forward_sim(named)
-        assert len(results) == len(candidates)
-        for candidate, (key, sim), (name, pair_boxes) in zip(candidates, named, results):
-            assert key == name
-            for box in pair_boxes:
-                box = tuple(int(v) for v in box)
-                match = self._to_match(candidate, box)
-                matches.append(match._replace(score=self.score(candidate, match, box, sim)))
+        if self._can_fuse_align():
+            n_boxes, boxes, box_max, status = self._aligned_boxes(candidates)
+            # the pairs the kernel did not finish (too long for its LDS state, too many boxes) take the reference's
+            # route and are spliced back in candidate order
+            left = [k for k in range(len(candidates)) if status[k] != 0]
+            by_host = dict(zip(left, self._reference_route([candidates[k] for k in left]))) if left else {}
+            for k, candidate in enumerate(candidates):
+                if k in by_host:
+                    matches += by_host[k]
+                    continue
+                for b in range(int(n_boxes[k])):
+                    match = self._to_match(candidate, [int(v) for v in boxes[k, b]])
+                    matches.append(match._replace(score=self._fused_score(candidate, box_max[k, b])))
+            return matches
+        for pair_matches in self._reference_route(candidates):
+            matches += pair_matches
         return matches
 
     def localize(self, candidate: CandidatePair) -> List[Match]:
