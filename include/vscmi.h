@@ -417,6 +417,38 @@ int vsc_align_forward_sim(const float* sims, const int64_t* sims_off, const int3
                           const vsc_align_params* params, int32_t* out_nbox, int32_t* out_boxes, float* out_boxmax,
                           int32_t* out_status, int device);
 
+/* ------------------------------------------------------------- match rows
+ * The last step of the reference's pipeline on the device: the padded box table of a localize_all batch becomes the
+ * rows of matches.csv (vsc/baseline/localization.py:66-73: query_start = ts_q[x1][0], query_end = ts_q[x2][1],
+ * ref_start = ts_r[y1][0], ref_end = ts_r[y2][1]) as dense columns, in the order localize_all emits its Match rows.
+ * Every output is a copy or a gather -- no arithmetic on values: the contract is exact, bit for bit.
+ *
+ * The per-frame [start, end] tables of both sides, float64 [total rows of that side][2] in ts_mem, copied into HBM and
+ * kept with the context (float32, float64 and integer sources up to 32 bits pass through float64 exactly; 1-D
+ * timestamps are handed over as (t, t) rows).  Either pointer may be NULL: that side is left as it is.
+ * vsc_tn_set_queries drops the query table, whose rows it replaces. */
+int vsc_tn_set_timestamps(vsc_tn_ctx_t* ctx, const double* q_ts, const double* r_ts, int ts_mem);
+/* The rows of one batch.  pair_q / pair_r (pairs_mem) and nbox / boxes / boxmax (in_mem) are the arguments and outputs
+ * of vsc_tn_localize or vsc_tn_align, host or device.  Row order: pair order, then box slot order.  Outputs (out_mem):
+ *   out_pair[cap]      int32   index of the row's pair in this call's pair list
+ *   out_box[cap][4]    int32   q_lo, r_lo, q_hi, r_hi (may be NULL)
+ *   out_score[cap]     fp32    the box's boxmax value
+ *   out_times[cap][4]  double  query_start, query_end, ref_start, ref_end
+ * *n_rows (host) receives the number of rows the inputs describe (the sum of nbox).  cap < that: VSC_ERR_CAPACITY and
+ * nothing is written.  All out_* NULL with cap == 0: VSC_OK, the count only (no timestamp table needed).
+ * Pairs that vsc_tn_align did not finish (status != 0) have nbox == 0 and contribute no rows.
+ *
+ * The row offsets are the exclusive prefix sum of nbox, computed on the device; the row pass handles one (pair, slot)
+ * per lane.  Stream and synchronisation as vsc_tn_localize: the call returns synchronised.
+ * Nothing is read outside the tables, whatever the inputs hold.  Guarded: a box count outside 0..VSC_TN_MAX_BOXES, a
+ * pair ordinal outside the context's videos, a corner outside [0, L) of its video, a missing timestamp table.  What
+ * lies in host memory is checked on the host before anything is launched; for device memory the kernels skip the
+ * offending rows and raise an error word.  Either way the call returns VSC_ERR_INVALID and the outputs are undefined.
+ * The launches are accounted under class 3 of the process-wide kernel-time accounting below. */
+int vsc_tn_match_rows(vsc_tn_ctx_t* ctx, const int32_t* pair_q, const int32_t* pair_r, int64_t n_pairs, int pairs_mem,
+                      const int32_t* nbox, const int32_t* boxes, const float* boxmax, int in_mem, int32_t* out_pair,
+                      int32_t* out_box, float* out_score, double* out_times, int64_t cap, int out_mem, int64_t* n_rows);
+
 /* ---------------------------------------------------------- instrumentation
  * Kernel-time accounting for bench.py: HIP events recorded on the handle's stream around the
  * dominant similarity kernel.  vsc_index_profile(idx, 1) enables it; vsc_index_profile_read
@@ -435,9 +467,9 @@ int vsc_index_profile_read_class(vsc_index_t* idx, int cls, double* ms, int64_t*
 /* Process-wide accounting of the entry points that own no index handle, same method (HIP events on the
  * stream the kernels run on): cls 0 = vsc_pair_max (vsc/candidates.py:24-40 on device hits), cls 1 = the
  * Temporal-Network launches of vsc_tn_localize / vsc_tn_forward_sim (vcsl.vta TN.forward_sim), cls 2 = the DTW / DP
- * launches of vsc_tn_align / vsc_align_forward_sim.
+ * launches of vsc_tn_align / vsc_align_forward_sim, cls 3 = the launches of vsc_tn_match_rows.
  * bytes = algorithmic bytes of the calls (4*dim*(Lq+Lr) per pair + boxes; 12 B per hit
- * + 20 B per pair).  bench.py only. */
+ * + 20 B per pair; match rows: 332 B per pair + 60 B written and 32 B gathered per row).  bench.py and scripts only. */
 int vsc_aux_profile(int enable);
 int vsc_aux_profile_read(int cls, double* ms, int64_t* calls, double* bytes, int reset);
 /* Counters of the last thresholded search on this handle: pairs the fp16 pre-filter passed on to

@@ -271,7 +271,7 @@ int vsc_aux_profile(int enable) {
     return VSC_OK;
 }
 int vsc_aux_profile_read(int cls, double* ms, int64_t* calls, double* bytes, int reset) {
-    if (cls < 0 || cls > 2) return VSC_ERR_INVALID;
+    if (cls < 0 || cls >= AUX_CLASSES) return VSC_ERR_INVALID;
     std::lock_guard<std::mutex> lk(g_aux.mu);
     if (ms) *ms = g_aux.ms[cls];
     if (calls) *calls = g_aux.n[cls];

@@ -1,5 +1,6 @@
 // C ABI of libvscmi.so, part 4: the entry points that own no index handle (vsc_pair_max, vsc_row_normalize) and the
-// Temporal-Network localisation contexts (vsc_tn_*) and the DTW / DP aligners on them (vsc_tn_align, vsc_align_forward_sim).
+// Temporal-Network localisation contexts (vsc_tn_*), the DTW / DP aligners on them (vsc_tn_align, vsc_align_forward_sim)
+// and the match-rows stage behind both (vsc_tn_set_timestamps, vsc_tn_match_rows).
 #include "api_internal.h"
 
 extern "C" {
@@ -457,6 +458,10 @@ struct vsc_tn_ctx {
     std::vector<int64_t> q_off, r_off;  // host copies
     DevBuf qfeat, rfeat, rfeat_h, d_qoff, d_roff;
     DevBuf d_pq, d_pr, d_work, d_nbox, d_boxes, d_bmax, d_status, slab, sims;
+    // match rows (vsc_tn_set_timestamps / vsc_tn_match_rows): the per-frame [start, end] tables of both sides as float64
+    // [rows][2], the scan's scratch and control words, and the row columns when the caller wants them on the host
+    DevBuf d_qts, d_rts, d_rowoff, d_tileoff, d_rowctl, d_rows[4];
+    bool has_qts = false, has_rts = false;
     Workspace ws;
     hipStream_t stream = nullptr;      // own_stream, or the caller's (vsc_tn_set_stream)
     hipStream_t own_stream = nullptr;
@@ -608,6 +613,7 @@ int vsc_tn_set_queries(vsc_tn_ctx_t* c, const float* qfeat, const int64_t* q_off
         return VSC_ERR_INVALID;
     }
     VSC_HIP(hipSetDevice(c->device));
+    c->has_qts = false;  // (the table described the rows that are being replaced: vsc_tn_set_timestamps)
     // everything that can fail (allocation, packing, upload) runs on local state first: the context keeps its old,
     // consistent query side if any of it does, and takes the new offsets only once the device holds the new rows
     std::vector<int64_t> off(q_off, q_off + n_qvid + 1);
@@ -643,6 +649,8 @@ int vsc_tn_destroy(vsc_tn_ctx_t* c) {
     c->qfeat.release(); c->rfeat.release(); c->rfeat_h.release(); c->d_qoff.release(); c->d_roff.release();
     c->d_pq.release(); c->d_pr.release(); c->d_work.release(); c->d_nbox.release();
     c->d_boxes.release(); c->d_bmax.release(); c->d_status.release(); c->slab.release(); c->sims.release();
+    c->d_qts.release(); c->d_rts.release(); c->d_rowoff.release(); c->d_tileoff.release(); c->d_rowctl.release();
+    for (auto& b : c->d_rows) b.release();
     c->ws.release();
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
@@ -901,6 +909,170 @@ int vsc_align_forward_sim(const float* sims, const int64_t* sims_off, const int3
     VSC_HIP(hipMemcpyAsync(out_boxmax, ws.out[2].p, (size_t)n_pairs * VSC_TN_MAX_BOXES * 4, hipMemcpyDeviceToHost, c->stream));
     VSC_HIP(hipMemcpyAsync(out_status, ws.out[3].p, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, c->stream));
     VSC_HIP(hipStreamSynchronize(c->stream));
+    return VSC_OK;
+}
+
+// ------------------------------------------------------------------------ match rows
+
+int vsc_tn_set_timestamps(vsc_tn_ctx_t* c, const double* q_ts, const double* r_ts, int ts_mem) {
+    if (!c) {
+        set_error("vsc_tn_set_timestamps: invalid argument");
+        return VSC_ERR_INVALID;
+    }
+    VSC_HIP(hipSetDevice(c->device));
+    const hipMemcpyKind kind = ts_mem == VSC_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    if (q_ts) {
+        const size_t bytes = (size_t)c->q_off.back() * 16;
+        c->has_qts = false;
+        VSC_TRY(c->d_qts.reserve(std::max<size_t>(bytes, 16)));
+        if (bytes) VSC_HIP(hipMemcpyAsync(c->d_qts.p, q_ts, bytes, kind, c->stream));
+    }
+    if (r_ts) {
+        const size_t bytes = (size_t)c->r_off.back() * 16;
+        c->has_rts = false;
+        VSC_TRY(c->d_rts.reserve(std::max<size_t>(bytes, 16)));
+        if (bytes) VSC_HIP(hipMemcpyAsync(c->d_rts.p, r_ts, bytes, kind, c->stream));
+    }
+    VSC_HIP(hipStreamSynchronize(c->stream));
+    c->has_qts = c->has_qts || q_ts != nullptr;
+    c->has_rts = c->has_rts || r_ts != nullptr;
+    return VSC_OK;
+}
+
+int vsc_tn_match_rows(vsc_tn_ctx_t* c, const int32_t* pair_q, const int32_t* pair_r, int64_t n_pairs, int pairs_mem,
+                      const int32_t* nbox, const int32_t* boxes, const float* boxmax, int in_mem, int32_t* out_pair,
+                      int32_t* out_box, float* out_score, double* out_times, int64_t cap, int out_mem, int64_t* n_rows) {
+    const bool count_only = cap == 0 && !out_pair && !out_box && !out_score && !out_times;
+    if (!n_rows || n_pairs < 0 || cap < 0 || (n_pairs > 0 && (!pair_q || !pair_r || !nbox || !boxes || !boxmax)) ||
+        (!count_only && (!out_pair || !out_score || !out_times))) {
+        set_error("vsc_tn_match_rows: invalid argument");
+        return VSC_ERR_INVALID;
+    }
+    *n_rows = 0;
+    // Host-memory inputs are checked here, before anything is launched; first what needs no context
+    const bool host_in = in_mem == VSC_MEM_HOST, host_pairs = pairs_mem == VSC_MEM_HOST;
+    if (host_in)
+        for (int64_t p = 0; p < n_pairs; ++p) {
+            if (nbox[p] < 0 || nbox[p] > VSC_TN_MAX_BOXES) {
+                set_error("vsc_tn_match_rows: pair %lld has a box count of %d (0..%d)", (long long)p, nbox[p], VSC_TN_MAX_BOXES);
+                return VSC_ERR_INVALID;
+            }
+            for (int x = 0; x < 4 * nbox[p]; ++x)
+                if (boxes[p * VSC_TN_MAX_BOXES * 4 + x] < 0) {
+                    set_error("vsc_tn_match_rows: pair %lld has a negative box corner", (long long)p);
+                    return VSC_ERR_INVALID;
+                }
+        }
+    if (host_pairs)
+        for (int64_t p = 0; p < n_pairs; ++p)
+            if (pair_q[p] < 0 || pair_r[p] < 0) {
+                set_error("vsc_tn_match_rows: pair %lld has video ordinal out of range", (long long)p);
+                return VSC_ERR_INVALID;
+            }
+    if (!c) {
+        set_error("vsc_tn_match_rows: invalid argument (no context)");
+        return VSC_ERR_INVALID;
+    }
+    if (host_pairs)
+        for (int64_t p = 0; p < n_pairs; ++p) {
+            const int32_t qv = pair_q[p], rv = pair_r[p];
+            if (qv >= c->n_qvid || rv >= c->n_rvid) {
+                set_error("vsc_tn_match_rows: pair %lld has video ordinal out of range", (long long)p);
+                return VSC_ERR_INVALID;
+            }
+            if (!host_in) continue;
+            const int64_t lq = c->q_off[qv + 1] - c->q_off[qv], lr = c->r_off[rv + 1] - c->r_off[rv];
+            const int32_t* b = boxes + p * VSC_TN_MAX_BOXES * 4;
+            for (int s = 0; s < nbox[p]; ++s, b += 4)
+                if (b[0] >= lq || b[2] >= lq || b[1] >= lr || b[3] >= lr) {
+                    set_error("vsc_tn_match_rows: box %d of pair %lld has a corner beyond its video (%lld x %lld frames)", s,
+                              (long long)p, (long long)lq, (long long)lr);
+                    return VSC_ERR_INVALID;
+                }
+        }
+    if (!count_only && (!c->has_qts || !c->has_rts)) {
+        set_error("vsc_tn_match_rows: the context has no %s timestamp table (vsc_tn_set_timestamps)", c->has_qts ? "reference" : "query");
+        return VSC_ERR_INVALID;
+    }
+    if (n_pairs == 0) return VSC_OK;
+    VSC_HIP(hipSetDevice(c->device));
+    MatchRowsArgs a;
+    memset(&a, 0, sizeof(a));
+    const void *dq, *dr, *dn, *db, *dm;
+    VSC_TRY(to_device(pair_q, (size_t)n_pairs * 4, pairs_mem, c->d_pq, &dq, c->stream));
+    VSC_TRY(to_device(pair_r, (size_t)n_pairs * 4, pairs_mem, c->d_pr, &dr, c->stream));
+    VSC_TRY(to_device(nbox, (size_t)n_pairs * 4, in_mem, c->d_nbox, &dn, c->stream));
+    VSC_TRY(to_device(boxes, (size_t)n_pairs * VSC_TN_MAX_BOXES * 16, in_mem, c->d_boxes, &db, c->stream));
+    VSC_TRY(to_device(boxmax, (size_t)n_pairs * VSC_TN_MAX_BOXES * 4, in_mem, c->d_bmax, &dm, c->stream));
+    VSC_TRY(c->d_rowoff.reserve((size_t)n_pairs * 4));
+    VSC_TRY(c->d_tileoff.reserve((size_t)match_rows_tiles(n_pairs) * 8));
+    VSC_TRY(c->d_rowctl.reserve(16));
+    a.pair_q = (const int32_t*)dq;
+    a.pair_r = (const int32_t*)dr;
+    a.n_pairs = n_pairs;
+    a.nbox = (const int32_t*)dn;
+    a.boxes = (const int32_t*)db;
+    a.boxmax = (const float*)dm;
+    a.q_off = c->d_qoff.as<int64_t>();
+    a.r_off = c->d_roff.as<int64_t>();
+    a.n_qvid = c->n_qvid;
+    a.n_rvid = c->n_rvid;
+    a.q_ts = c->d_qts.as<double>();
+    a.r_ts = c->d_rts.as<double>();
+    a.pair_off = c->d_rowoff.as<int32_t>();
+    a.tile_off = c->d_tileoff.as<int64_t>();
+    a.ctl = c->d_rowctl.as<int64_t>();
+    int64_t ctl[2] = {0, 0};
+    AuxTimer tm_scan, tm_emit;
+    tm_scan.begin(3, c->stream);
+    VSC_TRY(launch_match_rows_scan(a, c->stream));
+    tm_scan.end(4.0 * (double)n_pairs, c->stream);  // the box counts in
+    VSC_HIP(hipMemcpyAsync(ctl, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
+    VSC_HIP(hipStreamSynchronize(c->stream));  // (the host copies of host-memory inputs are read by the uploads above)
+    tm_scan.collect();
+    const int64_t total = ctl[0];
+    *n_rows = total;
+    if (ctl[1]) {
+        set_error("vsc_tn_match_rows: a pair has a box count outside 0..%d", VSC_TN_MAX_BOXES);
+        return VSC_ERR_INVALID;
+    }
+    if (count_only) return VSC_OK;
+    if (cap < total) {
+        set_error("vsc_tn_match_rows: output capacity %lld < %lld rows", (long long)cap, (long long)total);
+        return VSC_ERR_CAPACITY;
+    }
+    if (total == 0) return VSC_OK;
+    a.out_pair = out_pair;
+    a.out_box = out_box;
+    a.out_score = out_score;
+    a.out_times = out_times;
+    if (out_mem == VSC_MEM_HOST) {
+        const size_t width[4] = {4, 16, 4, 32};
+        for (int k = 0; k < 4; ++k) VSC_TRY(c->d_rows[k].reserve((size_t)total * width[k]));
+        a.out_pair = c->d_rows[0].as<int32_t>();
+        a.out_box = out_box ? c->d_rows[1].as<int32_t>() : nullptr;
+        a.out_score = c->d_rows[2].as<float>();
+        a.out_times = c->d_rows[3].as<double>();
+    }
+    tm_emit.begin(3, c->stream);
+    VSC_TRY(launch_match_rows_emit(a, c->stream));
+    // pair list + box table in, (pair, box, score, times) per row out, four timestamp gathers per row
+    tm_emit.end((8.0 + 20.0 * VSC_TN_MAX_BOXES) * (double)n_pairs + ((out_box ? 60.0 : 44.0) + 32.0) * (double)total, c->stream);
+    VSC_HIP(hipMemcpyAsync(ctl, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
+    VSC_HIP(hipStreamSynchronize(c->stream));
+    tm_emit.collect();
+    if (ctl[1]) {
+        set_error("vsc_tn_match_rows: a pair has %s (rows skipped)",
+                  (ctl[1] & 2) ? "a video ordinal out of range" : "a box corner outside its video");
+        return VSC_ERR_INVALID;
+    }
+    if (out_mem == VSC_MEM_HOST) {
+        VSC_HIP(hipMemcpyAsync(out_pair, a.out_pair, (size_t)total * 4, hipMemcpyDeviceToHost, c->stream));
+        if (out_box) VSC_HIP(hipMemcpyAsync(out_box, a.out_box, (size_t)total * 16, hipMemcpyDeviceToHost, c->stream));
+        VSC_HIP(hipMemcpyAsync(out_score, a.out_score, (size_t)total * 4, hipMemcpyDeviceToHost, c->stream));
+        VSC_HIP(hipMemcpyAsync(out_times, a.out_times, (size_t)total * 32, hipMemcpyDeviceToHost, c->stream));
+        VSC_HIP(hipStreamSynchronize(c->stream));
+    }
     return VSC_OK;
 }
 

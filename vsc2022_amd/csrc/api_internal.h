@@ -1,6 +1,6 @@
 // Internal declarations shared by the translation units of the C ABI (api.hip: handles, options, index upkeep;
 // api_search.hip: the thresholded searches; api_knn.hip: k-NN; api_aux.hip: pair-max, row normalisation, Temporal
-// Network).  Nothing here is exported: include/vscmi.h is the ABI.
+// Network, aligners, match rows).  Nothing here is exported: include/vscmi.h is the ABI.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -190,12 +190,13 @@ int prof_collect(vsc_index* idx);                                         // cal
 
 // Process-wide kernel-time accounting of the entry points that own no index handle (HIP events on the stream
 // the kernels run on; read after the call's own stream sync): 0 = vsc_pair_max, 1 = Temporal-Network launches,
-// 2 = DTW / DP launches.
+// 2 = DTW / DP launches, 3 = match-rows launches.
+constexpr int AUX_CLASSES = 4;
 struct AuxProf {
     bool on = false;
     std::mutex mu;
-    double ms[3] = {}, bytes[3] = {};
-    int64_t n[3] = {};
+    double ms[AUX_CLASSES] = {}, bytes[AUX_CLASSES] = {};
+    int64_t n[AUX_CLASSES] = {};
 };
 extern AuxProf g_aux;
 struct AuxTimer {

@@ -171,6 +171,17 @@ struct AlignArgs {
     const float* sims_in; const int64_t* sims_off; const int32_t* sims_lq; const int32_t* sims_lr;
     const _Float16* rfeat_h;  // as in TnPairArgs
 };
+// Match rows (match_rows.hip): the padded box table of a batch -> one dense row per box
+struct MatchRowsArgs {
+    const int32_t* pair_q; const int32_t* pair_r; int64_t n_pairs;
+    const int32_t* nbox; const int32_t* boxes; const float* boxmax;  // as vsc_tn_localize / vsc_tn_align write them
+    const int64_t* q_off; const int64_t* r_off; int64_t n_qvid, n_rvid;
+    const double* q_ts; const double* r_ts;  // [rows][2] start, end of every frame
+    int32_t* pair_off;  // [n_pairs] scratch: row offset of the pair inside its tile
+    int64_t* tile_off;  // [match_rows_tiles(n_pairs)] scratch: tile sums, then their exclusive scan
+    int64_t* ctl;       // [0] rows of the batch, [1] error word (bit 0 box count, bit 1 pair ordinal, bit 2 corner)
+    int32_t* out_pair; int32_t* out_box; float* out_score; double* out_times;  // out_box may be nullptr
+};
 // The working state of one pair, all of it in LDS: byte offsets into the workgroup's dynamic array and their sum.  The
 // kernel carves by the pair's own shape; a launch asks for the largest `total` among its pairs.
 //   both: tile   the similarity matrix, fp32 [lq][lr] (not in forward_sim mode: the caller's matrix is read in place)
@@ -268,6 +279,9 @@ size_t tn_state_bytes_host(int, int, int, int idx_bytes = 2);
 int launch_tn_pairs(const TnPairArgs&, size_t, hipStream_t);
 int launch_tn_sims(const TnSimsArgs&, hipStream_t);
 int launch_align_pairs(const AlignArgs&, size_t, hipStream_t);
+int64_t match_rows_tiles(int64_t n_pairs);
+int launch_match_rows_scan(const MatchRowsArgs&, hipStream_t);
+int launch_match_rows_emit(const MatchRowsArgs&, hipStream_t);
 // SQfp16 codec (codec_f16.hip)
 int launch_encode_rows(const void*, bool, int64_t, int, _Float16*, float*, int64_t, int64_t, int, bool, int*, hipStream_t);
 int launch_decode_rows(const _Float16*, int, bool, int64_t, int64_t, int64_t, float*, int, bool, hipStream_t);

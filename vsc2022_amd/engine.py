@@ -46,6 +46,14 @@ class MatchResult:
     matches_reference: bool = True
     tie_on_cut: bool = False         # s_K == s_(K+1) over the whole score matrix
     ties_dropped: bool = False       # ... and the reference's schedule ends on that very score: hits tied with it dropped
+    # match(rows=True): the match rows of the pairs this process localised, in (candidate, box slot) order -- the rows of
+    # matches.csv as device columns (include/vscmi.h, vsc_tn_match_rows).  None without rows=True
+    row_cand: Optional[torch.Tensor] = None    # [n_rows] int64 index into the candidate table
+    row_q: Optional[torch.Tensor] = None       # [n_rows] int32 query video ordinal (global)
+    row_r: Optional[torch.Tensor] = None       # [n_rows] int32 ref video ordinal
+    row_score: Optional[torch.Tensor] = None   # [n_rows] fp32: MaxSim - bias, or the candidate's score (box_score="candidate")
+    row_times: Optional[torch.Tensor] = None   # [n_rows, 4] float64 query_start, query_end, ref_start, ref_end
+    row_boxes: Optional[torch.Tensor] = None   # [n_rows, 4] int32 q_lo, r_lo, q_hi, r_hi
 
 
 def _dev_ptr(t: torch.Tensor) -> int:
@@ -155,7 +163,7 @@ class DeviceMatcher:
     """
 
     def __init__(self, ref_feats, r_off: np.ndarray, device: Optional[int] = None, tn_ref_feats=None, codec: str = "Flat",
-                 tn_codec: str = "Flat"):
+                 tn_codec: str = "Flat", r_ts=None):
         """codec: how the search index (and the column index of the column-sharded mode) stores the reference rows
         ("Flat" / "SQfp16", vsc.index.FlatIndex).  The codec belongs to the index: the Temporal-Network context keeps its
         own copy of the descriptors it is given, as localisation does in the reference.
@@ -164,7 +172,8 @@ class DeviceMatcher:
 
         tn_ref_feats: reference rows the ALIGNER sees when they differ from the rows that are searched
         (vsc/baseline/sscd_baseline.py:128-135: without score normalisation the reference searches the descriptors as they
-        are and localises on their L2-normalised copies)."""
+        are and localises on their L2-normalised copies).
+        r_ts: the reference videos' timestamps, [rows] or [rows, 2] (array or tensor), for `match(rows=True)`."""
         self._tn_codec_id = _lib.codec_id(tn_codec)  # (NotImplementedError for an unknown string before any device is needed)
         self.tn_codec = tn_codec
         self.device = _lib.default_device() if device is None else int(device)
@@ -187,11 +196,41 @@ class DeviceMatcher:
         self.row2r = torch.repeat_interleave(torch.arange(self.n_rvid, dtype=torch.int32, device=self.tdev), lens)
         self._tn = None
         self._bufs = {}
+        self._r_ts, self._r_ts_dtype = self._as_ts(r_ts, int(self.r_off[-1]))
+        self._q_ts, self._q_ts_dtype = None, None
 
     def _as_dev(self, x):
         if isinstance(x, torch.Tensor):
             return x.to(self.tdev, torch.float32).contiguous()
         return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(self.tdev)
+
+    def _as_ts(self, ts, rows: int):
+        """(float64 [rows, 2] start / end table in HBM, dtype of the source) of a timestamps argument; 1-D timestamps
+        become (t, t) rows, as VideoMetadata.get_timestamps returns them.  (None, None) for None."""
+        if ts is None:
+            return None, None
+        if isinstance(ts, torch.Tensor):
+            src = np.dtype(str(ts.dtype).replace("torch.", ""))
+            t = ts.to(self.tdev, torch.float64)
+        else:
+            ts = np.asarray(ts)
+            src = ts.dtype
+            t = torch.from_numpy(np.ascontiguousarray(ts, dtype=np.float64)).to(self.tdev)
+        if t.dim() == 1:
+            t = torch.stack([t, t], dim=1)
+        if t.dim() != 2 or t.shape[0] != rows or t.shape[1] != 2:
+            raise ValueError(f"timestamps: expected [{rows}] or [{rows}, 2], got {tuple(t.shape)}")
+        return t.contiguous(), src
+
+    def _upload_ts(self, q: bool, r: bool):
+        """hand the tables to the Temporal-Network context (which keeps its own copy)"""
+        q_t = self._q_ts if q else None
+        r_t = self._r_ts if r else None
+        if q_t is None and r_t is None:
+            return
+        self._order()
+        _lib.check(_lib.lib().vsc_tn_set_timestamps(self._tn, None if q_t is None else _dev_ptr(q_t),
+                                                    None if r_t is None else _dev_ptr(r_t), _lib.MEM_DEVICE))
 
     def _buf(self, name, n, dtype, cols=None):
         shape = (n,) if cols is None else (n,) + tuple(cols)
@@ -202,9 +241,12 @@ class DeviceMatcher:
         return b
 
     # ---- queries
-    def set_queries(self, q_feats, q_off: np.ndarray, tn_q_feats=None):
+    def set_queries(self, q_feats, q_off: np.ndarray, tn_q_feats=None, q_ts=None):
+        """q_ts: the query videos' timestamps, [rows] or [rows, 2] (array or tensor), for `match(rows=True)`; without it
+        the new query set has none."""
         self.q_off = np.ascontiguousarray(q_off, dtype=np.int64)
         self.n_qvid = len(self.q_off) - 1
+        self._q_ts, self._q_ts_dtype = self._as_ts(q_ts, int(self.q_off[-1]))
         self.q_feats = self._as_dev(q_feats)
         self.tn_q_feats = self.q_feats if tn_q_feats is None else self._as_dev(tn_q_feats)
         lens = torch.from_numpy(np.diff(self.q_off)).to(self.tdev)
@@ -214,6 +256,7 @@ class DeviceMatcher:
             self._order()
             _lib.check(_lib.lib().vsc_tn_set_queries(self._tn, _dev_ptr(self.tn_q_feats), self.q_off.ctypes.data,
                                                      self.n_qvid, _lib.MEM_DEVICE))
+            self._upload_ts(q=True, r=False)   # (vsc_tn_set_queries dropped the old query table)
             return
         torch.cuda.synchronize(self.tdev)  # (once: a fresh context packs its rows on its own stream, bound below)
         ctx = ctypes.c_void_p()
@@ -224,6 +267,7 @@ class DeviceMatcher:
         self._tn = ctx
         self._tn_stream = None
         self._order()
+        self._upload_ts(q=True, r=True)
 
     def _order(self):
         """torch's queued work before the library's next reads: (re)bind the handles to torch's current stream, or
@@ -328,14 +372,23 @@ class DeviceMatcher:
 
     # ---- the whole hot path
     def match(self, n_qvid_global: Optional[int] = None, qvid_base: int = 0, row_base: int = 0, group=None,
-              bias: float = 0.0, localize: bool = True) -> MatchResult:
+              bias: float = 0.0, localize: bool = True, rows: bool = False, box_score: str = "maxsim") -> MatchResult:
         """search -> candidates -> localisation for the resident queries.
 
         Single process: n_qvid_global is None.  Sharded (one process per GPU): this rank owns the
         query videos [qvid_base, qvid_base + n_qvid) / rows [row_base, ...) of a global query set
         of n_qvid_global videos; the two global cuts are resolved with vsc2022_amd.dist.
         localize=False stops after the candidate table (vsc/descriptor_eval_lib.py:42-49: no aligner).
+        rows=True ends the step where the reference ends it: the result also carries the match rows of the pairs this
+        process localised (MatchResult.row_*: candidate index, video ordinals, score, the four timestamps), made on the
+        device from the box table and the timestamps given to the constructor / `set_queries`; `match_table` turns them
+        into a MatchTable.  box_score: "maxsim" (the kernel's box score) or "candidate" (the candidate's score).
         """
+        if box_score not in ("maxsim", "candidate"):
+            raise ValueError(f"box_score {box_score!r}: 'maxsim' or 'candidate'")
+        if rows and (getattr(self, "_q_ts", None) is None or getattr(self, "_r_ts", None) is None):
+            raise ValueError("match(rows=True) needs the timestamps of both sides: DeviceMatcher(..., r_ts=...) and "
+                             "set_queries(..., q_ts=...)")
         sharded = n_qvid_global is not None and torch.distributed.is_initialized() and \
             (torch.distributed.get_world_size(group) > 1 or os.environ.get("VSC_FORCE_SHARDED") == "1")
         nq_glob = n_qvid_global if n_qvid_global is not None else self.n_qvid
@@ -349,9 +402,10 @@ class DeviceMatcher:
             n_cand = min(int(ps.numel()), n_cand_cut)
             n_loc = min(n_cand, n_loc_cut) if localize else 0
             nbox, boxes, bmax = self.localize(pq[:n_loc], pr[:n_loc], bias)
-            return MatchResult(int(hs.numel()), int(ps.numel()), n_cand, n_loc, int(nbox.sum().item()),
-                               pq[:n_cand], pr[:n_cand], ps[:n_cand],
-                               torch.arange(n_loc, device=self.tdev), nbox, boxes, bmax, radius)
+            res = MatchResult(int(hs.numel()), int(ps.numel()), n_cand, n_loc, int(nbox.sum().item()),
+                              pq[:n_cand], pr[:n_cand], ps[:n_cand],
+                              torch.arange(n_loc, device=self.tdev), nbox, boxes, bmax, radius)
+            return self._with_rows(res, pq[:n_loc], pr[:n_loc], res.n_matches, box_score) if rows else res
         # The reference's schedule itself, over query shards (vsc2022_amd/dist.py, module docstring + emulate_schedule): a
         # proof about the K cut cannot replace it -- at BASELINE's sizes a tie on the cut is certain.
         hi, hj, hs, radius, info = self.sharded_schedule_search(K, nq_glob_rows=None, row_base=row_base, group=group)
@@ -370,11 +424,60 @@ class DeviceMatcher:
         mine = (cands.q_vid[:n_loc] >= qvid_base) & (cands.q_vid[:n_loc] < qvid_base + self.n_qvid)
         loc_index = torch.nonzero(mine).flatten()
         nbox, boxes, bmax = self.localize(cands.q_vid[loc_index] - qvid_base, cands.r_vid[loc_index], bias)
-        n_matches = vdist.all_reduce_sum_int(int(nbox.sum().item()), self.tdev, group)
+        n_here = int(nbox.sum().item())
+        n_matches = vdist.all_reduce_sum_int(n_here, self.tdev, group)
         n_hits = vdist.all_reduce_sum_int(n_take, self.tdev, group)
-        return MatchResult(n_hits, int(ps.numel()), n_cand, n_loc, n_matches,
-                           cands.q_vid, cands.r_vid, cands.score, loc_index, nbox, boxes, bmax, radius,
-                           matches_reference=proven, tie_on_cut=tie, ties_dropped=dropped)
+        res = MatchResult(n_hits, int(ps.numel()), n_cand, n_loc, n_matches,
+                          cands.q_vid, cands.r_vid, cands.score, loc_index, nbox, boxes, bmax, radius,
+                          matches_reference=proven, tie_on_cut=tie, ties_dropped=dropped)
+        if rows:
+            self._with_rows(res, cands.q_vid[loc_index] - qvid_base, cands.r_vid[loc_index], n_here, box_score)
+        return res
+
+    # ---- the rows of matches.csv
+    def match_rows(self, pair_q: torch.Tensor, pair_r: torch.Tensor, nbox, boxes, bmax, n_rows: Optional[int] = None):
+        """vsc/baseline/localization.py:66-73 for a device-resident box table (LOCAL query ordinals): (pair index int32
+        [n], corners int32 [n, 4], box score fp32 [n], times float64 [n, 4]) in (pair, box slot) order, by libvscmi's
+        vsc_tn_match_rows.  n_rows: the number of rows when the caller knows it (nbox.sum())."""
+        n = int(pair_q.numel())
+        cap = int(nbox.sum().item()) if n_rows is None else int(n_rows)
+        out_pair = torch.empty(cap, dtype=torch.int32, device=self.tdev)
+        out_box = torch.empty((cap, 4), dtype=torch.int32, device=self.tdev)
+        out_score = torch.empty(cap, dtype=torch.float32, device=self.tdev)
+        out_times = torch.empty((cap, 4), dtype=torch.float64, device=self.tdev)
+        if n and cap:
+            pq, pr = pair_q.to(torch.int32).contiguous(), pair_r.to(torch.int32).contiguous()
+            nbox, boxes, bmax = nbox.contiguous(), boxes.contiguous(), bmax.contiguous()
+            got = ctypes.c_int64(0)
+            self._order()
+            _lib.check(_lib.lib().vsc_tn_match_rows(
+                self._tn, _dev_ptr(pq), _dev_ptr(pr), n, _lib.MEM_DEVICE, _dev_ptr(nbox), _dev_ptr(boxes), _dev_ptr(bmax),
+                _lib.MEM_DEVICE, _dev_ptr(out_pair), _dev_ptr(out_box), _dev_ptr(out_score), _dev_ptr(out_times), cap,
+                _lib.MEM_DEVICE, ctypes.byref(got)))
+            assert got.value == cap, (got.value, cap)
+        return out_pair, out_box, out_score, out_times
+
+    def _with_rows(self, res: MatchResult, pair_q, pair_r, n_rows: int, box_score: str) -> MatchResult:
+        pair, corners, score, times = self.match_rows(pair_q, pair_r, res.nbox, res.boxes, res.box_score, n_rows)
+        res.row_cand = res.loc_index.to(torch.int64)[pair.to(torch.int64)]
+        res.row_q, res.row_r = res.cand_q[res.row_cand], res.cand_r[res.row_cand]
+        res.row_score = score if box_score == "maxsim" else res.cand_score[res.row_cand]
+        res.row_times, res.row_boxes = times, corners
+        return res
+
+    def match_table(self, res: MatchResult, q_ids, r_ids):
+        """The rows of `match(rows=True)` as a vsc.metrics.MatchTable: one device-to-host copy per column, ids looked up by
+        (global) video ordinal, times cast back to the dtype of the timestamps they came from.  No per-row Python."""
+        from vsc2022_amd.vsc.metrics import MatchTable
+
+        if res.row_cand is None:
+            raise ValueError("match_table needs a result of match(rows=True)")
+        times = res.row_times.cpu().numpy()
+        q_t, r_t = self._q_ts_dtype, self._r_ts_dtype
+        return MatchTable(MatchTable._ids(q_ids)[res.row_q.cpu().numpy()], MatchTable._ids(r_ids)[res.row_r.cpu().numpy()],
+                          res.row_score.cpu().numpy(), times[:, 0].astype(q_t), times[:, 1].astype(q_t),
+                          times[:, 2].astype(r_t), times[:, 3].astype(r_t), res.row_cand.cpu().numpy(),
+                          res.row_boxes.cpu().numpy())
 
     # ---- the query-sharded search
     def _rows_above(self, rows: torch.Tensor, radius: float, budget: int, index: Optional[FlatIndex] = None):

@@ -13,6 +13,9 @@ the host merely converts box corners to timestamps.  A subclass that overrides `
 `similarity`) in a way the fused kernel cannot know is still honoured: it falls back to the
 reference's route -- similarity matrices on the host, `self.model.forward_sim(...)`,
 `self.score(...)` per box.
+
+`localize_table` returns the rows of `localize_all` as a `vsc.metrics.MatchTable`: the timestamp tables are uploaded with
+the descriptors, and on the fused routes the box -> timestamp conversion is device work too (libvscmi vsc_tn_match_rows).
 """
 import abc
 import ctypes
@@ -22,7 +25,7 @@ import numpy as np
 
 from vsc2022_amd import _lib
 from vsc2022_amd.vsc.index import VideoFeature, VideoLayout
-from vsc2022_amd.vsc.metrics import CandidatePair, Match
+from vsc2022_amd.vsc.metrics import CandidatePair, Match, MatchTable, _column
 
 
 class Localization(abc.ABC):
@@ -35,6 +38,28 @@ class Localization(abc.ABC):
         for candidate in candidates:
             out += self.localize(candidate)
         return out
+
+
+def _timestamp_rows(videos: Sequence[VideoFeature]) -> np.ndarray:
+    """float64 [rows, 2] = (start, end) of every frame of the videos, in order; 1-D timestamps become (t, t) rows, as
+    `get_timestamps` returns them.  float32, float64 and integers up to 32 bits are exact in float64."""
+    parts = []
+    for v in videos:
+        t = np.asarray(v.timestamps)
+        if t.dtype.kind not in "fiu":
+            raise TypeError(f"video {v.video_id!r}: timestamps of dtype {t.dtype} cannot be kept on the device")
+        parts.append(np.stack([t, t], axis=1) if t.ndim == 1 else t[:, :2])
+    if not parts:
+        return np.zeros((0, 2), dtype=np.float64)
+    return np.ascontiguousarray(np.concatenate([p.astype(np.float64) for p in parts], axis=0))
+
+
+def _time_dtype(videos: Sequence[VideoFeature], used: np.ndarray) -> np.dtype:
+    """dtype of a time column: that of the `timestamps` arrays of the videos that have rows (of all videos when none has),
+    their common dtype when they disagree (float32 with float64: float64) -- what a list of their scalars becomes."""
+    pool = [videos[k] for k in used] if len(used) else list(videos)
+    kinds = {np.asarray(v.timestamps).dtype for v in pool}
+    return np.result_type(*kinds) if kinds else np.dtype(np.float64)
 
 
 class LocalizationWithMetadata(Localization):
@@ -71,6 +96,15 @@ class LocalizationWithMetadata(Localization):
             q_rows.ctypes.data if q_rows.size else None, q_layout.offsets.ctypes.data, len(self._q_videos),
             r_rows.ctypes.data if r_rows.size else None, int(r_half), r_layout.offsets.ctypes.data, len(self._r_videos),
             int(dim), _lib.MEM_HOST, _lib.MEM_HOST, self._ref_codec_id, self.device, ctypes.byref(self._ctx)))
+        # the per-frame [start, end] tables go down with the descriptors (include/vscmi.h, match rows).  Timestamps the
+        # device table cannot hold (not numeric) leave `localize_all` as it was; `localize_table` then says why it cannot run
+        self._ts_error = None
+        try:
+            q_ts, r_ts = _timestamp_rows(self._q_videos), _timestamp_rows(self._r_videos)
+        except (TypeError, ValueError) as exc:
+            self._ts_error = exc
+            return
+        _lib.check(_lib.lib().vsc_tn_set_timestamps(self._ctx, q_ts.ctypes.data, r_ts.ctypes.data, _lib.MEM_HOST))
 
     @property
     def ref_bytes(self) -> int:
@@ -215,11 +249,87 @@ class VCSLLocalization(LocalizationWithMetadata):
     def localize(self, candidate: CandidatePair) -> List[Match]:
         return self.localize_all([candidate])
 
+    # -- the same rows as columns ---------------------------------------------------------------
+    def _device_rows(self, candidates, pair_q, pair_r, n_boxes, boxes, box_max) -> MatchTable:
+        """The box table of a batch -> its match rows, by the engine's match-rows stage (vsc_tn_match_rows: row offsets,
+        timestamp gathers and the dense table are device work); ids and column dtypes are attached here."""
+        if self._ts_error is not None:
+            raise ValueError(f"localize_table needs numeric timestamps: {self._ts_error}")
+        n = len(candidates)
+        cap = int(n_boxes.sum(dtype=np.int64))
+        pair = np.empty(cap, dtype=np.int32)
+        corners = np.empty((cap, 4), dtype=np.int32)
+        score = np.empty(cap, dtype=np.float32)
+        times = np.empty((cap, 4), dtype=np.float64)
+        n_rows = ctypes.c_int64(0)
+        _lib.check(_lib.lib().vsc_tn_match_rows(
+            self._ctx, pair_q.ctypes.data, pair_r.ctypes.data, n, _lib.MEM_HOST, n_boxes.ctypes.data, boxes.ctypes.data,
+            box_max.ctypes.data, _lib.MEM_HOST, pair.ctypes.data, corners.ctypes.data, score.ctypes.data,
+            times.ctypes.data, cap, _lib.MEM_HOST, ctypes.byref(n_rows)))
+        assert n_rows.value == cap
+        q_ord, r_ord = pair_q[pair], pair_r[pair]
+        q_t = _time_dtype(self._q_videos, np.unique(q_ord))
+        r_t = _time_dtype(self._r_videos, np.unique(r_ord))
+        q_ids = MatchTable._ids(v.video_id for v in self._q_videos)
+        r_ids = MatchTable._ids(v.video_id for v in self._r_videos)
+        return MatchTable(q_ids[q_ord], r_ids[r_ord], self._fused_score_column(candidates, pair, score),
+                          times[:, 0].astype(q_t), times[:, 1].astype(q_t), times[:, 2].astype(r_t),
+                          times[:, 3].astype(r_t), pair.astype(np.int64), corners)
+
+    def _reference_table(self, candidates: Sequence[CandidatePair], pair_index: Sequence[int]) -> MatchTable:
+        """`_reference_route` with the rows collected as columns (pair_index: the candidates' positions in the batch)."""
+        named = [(f"{c.query_id}-{c.ref_id}", self.similarity(c)) for c in candidates]
+        results = self.model.forward_sim(named)
+        assert len(results) == len(candidates)
+        matches, pair, corners = [], [], []
+        for k, candidate, (key, sim), (name, pair_boxes) in zip(pair_index, candidates, named, results):
+            assert key == name
+            for box in pair_boxes:
+                box = tuple(int(v) for v in box)
+                match = self._to_match(candidate, box)
+                matches.append(match._replace(score=self.score(candidate, match, box, sim)))
+                pair.append(k)
+                corners.append(box)
+        return MatchTable.from_matches(matches, pair=pair, boxes=corners)
+
+    def localize_table(self, candidates: List[CandidatePair]) -> MatchTable:
+        """`localize_all(candidates)` as a MatchTable: the same rows in the same order, values and dtypes included
+        (`localize_table(c).to_matches() == localize_all(c)`, and `write_csv` writes the same file).  On the fused
+        routes the timestamps are gathered on the device and there is no per-box Python."""
+        candidates = candidates if hasattr(candidates, "columns") else list(candidates)
+        n = len(candidates)
+        if n == 0:
+            return MatchTable.empty()
+        if self._can_fuse():
+            n_boxes, boxes, box_max = self._fused_boxes(candidates)
+            pair_q, pair_r = self._pair_ordinals(candidates)
+            return self._device_rows(candidates, pair_q, pair_r, n_boxes, boxes, box_max)
+        if self._can_fuse_align():
+            n_boxes, boxes, box_max, status = self._aligned_boxes(candidates)
+            pair_q, pair_r = self._pair_ordinals(candidates)
+            table = self._device_rows(candidates, pair_q, pair_r, n_boxes, boxes, box_max)  # (nbox = 0 where status != 0)
+            left = [k for k in range(n) if status[k] != 0]
+            if not left:
+                return table
+            # the pairs the kernel did not finish take the reference's route and are spliced back in candidate order
+            both = MatchTable.concat([table, self._reference_table([candidates[k] for k in left], left)])
+            return both.take(np.argsort(both.pair, kind="stable"))
+        return self._reference_table(candidates, range(n))
+
+    def _pair_ordinals(self, candidates):
+        n = len(candidates)
+        return (np.fromiter((self._q_ordinal[c.query_id] for c in candidates), dtype=np.int32, count=n),
+                np.fromiter((self._r_ordinal[c.ref_id] for c in candidates), dtype=np.int32, count=n))
+
     def score(self, candidate: CandidatePair, match: Match, box, similarity) -> float:
         return 1.0
 
     def _fused_score(self, candidate: CandidatePair, box_max) -> float:
         return 1.0
+
+    def _fused_score_column(self, candidates, pair: np.ndarray, box_max: np.ndarray) -> np.ndarray:
+        """`_fused_score` of every row at once."""
+        return np.ones(len(pair), dtype=np.float64)
 
 
 class VCSLLocalizationMaxSim(VCSLLocalization):
@@ -233,6 +343,9 @@ class VCSLLocalizationMaxSim(VCSLLocalization):
     def _fused_score(self, candidate: CandidatePair, box_max) -> float:
         return box_max  # computed by the kernel as max(sims[x1:x2, y1:y2]) - bias
 
+    def _fused_score_column(self, candidates, pair, box_max):
+        return box_max
+
 
 class VCSLLocalizationCandidateScore(VCSLLocalization):
     """Box score = the retrieval score of the candidate pair."""
@@ -242,3 +355,9 @@ class VCSLLocalizationCandidateScore(VCSLLocalization):
 
     def _fused_score(self, candidate: CandidatePair, box_max) -> float:
         return candidate.score
+
+    def _fused_score_column(self, candidates, pair, box_max):
+        # (the scores keep the type they have in the candidates: float32 from the engine's lists, float64 from Python floats)
+        columns = getattr(candidates, "columns", None)
+        scores = np.asarray(columns()[2]) if columns is not None else _column([c.score for c in candidates])
+        return scores[pair]

@@ -85,6 +85,18 @@ def localize_and_verify(queries: List[VideoFeature], refs: List[VideoFeature], c
     return found
 
 
+def localize_table(queries: List[VideoFeature], refs: List[VideoFeature], candidates: Sequence[M.CandidatePair],
+                   localize_per_query: float = CONSTANTS.localize_per_query,
+                   score_normalization: bool = False) -> M.MatchTable:
+    """`localize_and_verify` as a MatchTable: the same rows in the same order, and `write_csv` writes the same
+    matches.csv.  Pairs are independent, so the whole list goes down as one batch instead of 512-pair ones; the
+    timestamps are gathered on the device (VCSLLocalization.localize_table)."""
+    todo = candidates[: int(len(queries) * localize_per_query)]
+    table = _aligner(queries, refs, score_normalization).localize_table(todo)
+    logger.info("localised %d pairs, %d segments", len(todo), len(table))
+    return table
+
+
 def match(queries: List[VideoFeature], refs: List[VideoFeature], output_path: str,
           score_normalization: bool = False) -> Tuple[str, str]:
     """Runs the matching pipeline; returns the paths of candidates.csv and matches.csv."""

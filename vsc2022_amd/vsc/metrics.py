@@ -224,6 +224,104 @@ class Match(NamedTuple):
         return [cls(**row) for row in table.to_dict("records")]
 
 
+def _column(values, like: Optional[np.ndarray] = None) -> np.ndarray:
+    """A list of scalars as an array of the dtype those scalars carry (np.float32 scalars -> float32, Python floats ->
+    float64); an empty list takes the dtype of `like`."""
+    values = list(values)
+    if not values:
+        return np.zeros(0, dtype=like.dtype if like is not None else np.float64)
+    return np.asarray(values)
+
+
+@dataclasses.dataclass
+class MatchTable:
+    """The rows of a `List[Match]` as columns: what the match-rows stage of the engine returns (include/vscmi.h,
+    vsc_tn_match_rows) and what `write_csv` needs.  No per-row Python anywhere but in `to_matches`.
+
+    Every column keeps the dtype the scalar route yields -- scores float32 from the MaxSim kernel, float64 from Python
+    floats; times in the dtype of the videos' `timestamps` arrays -- because the CSV text depends on it: `write_csv`
+    writes byte for byte what `Match.write_csv(table.to_matches(), file)` writes.
+
+    pair: index of the row's candidate in the candidate list the table came from; boxes: [n, 4] int32 frame indices
+    q_lo, r_lo, q_hi, r_hi (inclusive ends)."""
+
+    query_id: np.ndarray
+    ref_id: np.ndarray
+    score: np.ndarray
+    query_start: np.ndarray
+    query_end: np.ndarray
+    ref_start: np.ndarray
+    ref_end: np.ndarray
+    pair: np.ndarray
+    boxes: np.ndarray
+
+    def __post_init__(self):
+        n = len(self.score)
+        for field in Match._fields + ("pair", "boxes"):
+            assert len(getattr(self, field)) == n, f"column {field} has {len(getattr(self, field))} rows, score has {n}"
+
+    def __len__(self):
+        return len(self.score)
+
+    @staticmethod
+    def _ids(values) -> np.ndarray:
+        values = list(values)
+        out = np.empty(len(values), dtype=object)  # (never a numpy string array: ids keep their own type)
+        out[:] = values
+        return out
+
+    @classmethod
+    def empty(cls, score_dtype=np.float64, time_dtype=np.float64) -> "MatchTable":
+        t = np.zeros(0, dtype=time_dtype)
+        return cls(cls._ids([]), cls._ids([]), np.zeros(0, dtype=score_dtype), t, t.copy(), t.copy(), t.copy(),
+                   np.zeros(0, dtype=np.int64), np.zeros((0, 4), dtype=np.int32))
+
+    @classmethod
+    def from_matches(cls, matches: Collection[Match], pair=None, boxes=None) -> "MatchTable":
+        """Columns of a list of Match (the host routes); pair / boxes default to -1."""
+        matches = list(matches)
+        n = len(matches)
+        return cls(cls._ids(m.query_id for m in matches), cls._ids(m.ref_id for m in matches),
+                   _column(m.score for m in matches), _column(m.query_start for m in matches),
+                   _column(m.query_end for m in matches), _column(m.ref_start for m in matches),
+                   _column(m.ref_end for m in matches),
+                   np.full(n, -1, dtype=np.int64) if pair is None else np.asarray(pair, dtype=np.int64).reshape(n),
+                   np.full((n, 4), -1, dtype=np.int32) if boxes is None else np.asarray(boxes, dtype=np.int32).reshape(n, 4))
+
+    def to_matches(self) -> List[Match]:
+        """The rows as Match tuples; every value is the numpy scalar of its column (as the per-box route yields them)."""
+        return [Match(*row) for row in zip(*(getattr(self, field) for field in Match._fields))]
+
+    def to_dataframe(self):
+        return _pandas().DataFrame({field: getattr(self, field) for field in Match._fields}, columns=Match._fields)
+
+    def write_csv(self, file: Union[str, TextIO]):
+        self.to_dataframe().to_csv(file, index=False)
+
+    def take(self, index) -> "MatchTable":
+        """The rows `index` (an index array or a boolean mask), in that order."""
+        return MatchTable(*(getattr(self, f.name)[index] for f in dataclasses.fields(self)))
+
+    @classmethod
+    def concat(cls, tables: Iterable["MatchTable"], pair_offsets: Optional[Iterable[int]] = None) -> "MatchTable":
+        """Tables one after the other.  pair_offsets: added to each table's `pair` column (batches of one candidate
+        list).  Empty tables do not vote on a column's dtype, as rows that do not exist cannot in a list of Match."""
+        tables = list(tables)
+        offsets = [0] * len(tables) if pair_offsets is None else [int(o) for o in pair_offsets]
+        assert len(offsets) == len(tables)
+        if not tables:
+            return cls.empty()
+        voting = [(t, o) for t, o in zip(tables, offsets) if len(t)] or [(tables[0], offsets[0])]
+        columns = []
+        for f in dataclasses.fields(cls):
+            parts = [getattr(t, f.name) + o if f.name == "pair" else getattr(t, f.name) for t, o in voting]
+            columns.append(parts[0] if len(parts) == 1 else np.concatenate(parts, axis=0))
+        return cls(*columns)
+
+    def __add__(self, other: "MatchTable") -> "MatchTable":
+        return MatchTable.concat([self, other])
+
+
 class VideoPair:
     """Running overlap statistics of one (query, ref) pair (metrics.py:238-301).
 
