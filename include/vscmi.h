@@ -449,6 +449,41 @@ int vsc_tn_match_rows(vsc_tn_ctx_t* ctx, const int32_t* pair_q, const int32_t* p
                       const int32_t* nbox, const int32_t* boxes, const float* boxmax, int in_mem, int32_t* out_pair,
                       int32_t* out_box, float* out_score, double* out_times, int64_t cap, int out_mem, int64_t* n_rows);
 
+/* ------------------------------------------------------------- segment AP of the matching track
+ * vsc/metrics.py match_metric on the device, up to its last few vector operations: ground-truth rows and prediction rows
+ * -> per group of equal scores, in descending score order, the score and the four running sums the metric divides
+ * (intersection with the ground truth on the query and the reference axis, covered length on both), + the ground truth's
+ * length per axis.  The caller finishes with r = sqrt((iq / tq) * (ir / tr)), p = sqrt((iq / cq) * (ir / cr)),
+ * ap = sum p * diff(r).  The contract is exact: every value is the float64 the host's walk computes, operation for
+ * operation and in its order (ranking: stable, descending, -0.0 and 0.0 one key; per pair the coalesced interval lists of
+ * `VideoPair.add_prediction`; the sums strictly in rank order) -- tests/match_metric_ref.py restates it.
+ *
+ * Rows carry the ordinal of their (query, ref) pair, 0 <= ordinal < n_pairs, any numbering:
+ *   gt_pair[n_gt] int32, gt_times[n_gt][4] double (query_start, query_end, ref_start, ref_end), gt_first[n_gt_pairs]
+ *   int32 = the ordinals of the ground truth's pairs in first-appearance order, the order their lengths are summed in
+ *   (NULL: 0, 1, ..., n_gt_pairs - 1) -- all three in gt_mem;
+ *   pred_pair[n_pred] int32, pred_score[n_pred] double, pred_times[n_pred][4] double in pred_mem.
+ * Outputs, host memory: out_score[cap], out_sums[cap][4] (iq, ir, cq, cr at each group end), *n_groups, gt_len[2]
+ * (tq, tr), stats[8] (may be NULL) = pairs evaluated from LDS, pairs evaluated from an HBM slab (more than 320 rows),
+ * prediction rows, groups; then the kernel time of the sorts, the pair kernels and the ordered sums in microseconds (HIP
+ * events, 0 unless vsc_aux_profile is on) and a reserved 0.  cap < the number of groups: VSC_ERR_CAPACITY, *n_groups is
+ * set and nothing else is written.
+ *
+ * Nothing is read outside the tables, whatever the inputs hold.  Guarded on the device (an error word, VSC_ERR_INVALID,
+ * outputs untouched): a pair ordinal outside [0, n_pairs), a non-finite score or time, end < start, and a pair with
+ * more than VSC_METRIC_MAX_PAIR_ROWS rows (predictions + ground-truth segments).  One wave evaluates a pair and its
+ * work is quadratic in the pair's rows (a counting sort of N^2 / 64 comparisons per lane and axis, then rows / 64 walks
+ * over the N-entry lists, read from HBM above 320 rows): a fraction of a second at the bound by that count (estimated,
+ * not measured), a minute at ten times as many -- so such a table is refused instead of holding a shared GPU.  The
+ * challenge's tables have a handful of rows per pair.
+ * Handle-less family: runs on the stream of vsc_set_aux_stream and returns synchronised.  The library keeps its scratch
+ * for the call (about 100 bytes of HBM per prediction row of the largest call so far) with the device's context. */
+#define VSC_METRIC_MAX_PAIR_ROWS 8192
+int vsc_match_metric(const int32_t* gt_pair, const double* gt_times, int64_t n_gt, const int32_t* gt_first, int64_t n_gt_pairs,
+                     int gt_mem, const int32_t* pred_pair, const double* pred_score, const double* pred_times, int64_t n_pred,
+                     int pred_mem, int64_t n_pairs, double* out_score, double* out_sums, int64_t cap, int64_t* n_groups,
+                     double* gt_len, int64_t* stats, int device);
+
 /* ---------------------------------------------------------- instrumentation
  * Kernel-time accounting for bench.py: HIP events recorded on the handle's stream around the
  * dominant similarity kernel.  vsc_index_profile(idx, 1) enables it; vsc_index_profile_read

@@ -37,6 +37,7 @@ TN_MAX_BOXES = 16
 # DTW / DP aligners on the device (vsc_tn_align, vsc_align_forward_sim)
 ALIGN_DTW = 1
 ALIGN_DP = 2
+METRIC_MAX_PAIR_ROWS = 8192  # VSC_METRIC_MAX_PAIR_ROWS: predictions + ground-truth rows of one (query, ref) pair
 ALIGN_MAX_CELLS = 9216  # VSC_ALIGN_MAX_CELLS: lq * lr of the largest pair whose working state fits LDS
 
 # every symbol include/vscmi.h declares
@@ -48,7 +49,7 @@ EXPORTS = (
     "vsc_index_range_search", "vsc_index_global_topk", "vsc_index_global_topk_seeded", "vsc_index_candidates", "vsc_pair_max", "vsc_sort_hits", "vsc_row_normalize",
     "vsc_score_histogram", "vsc_score_pick", "vsc_filter_hits", "vsc_argsort_scores", "vsc_merge_topk",
     "vsc_tn_create", "vsc_tn_create_codec", "vsc_tn_ref_bytes", "vsc_tn_set_queries", "vsc_tn_destroy", "vsc_tn_localize", "vsc_tn_forward_sim", "vsc_tn_similarity",
-    "vsc_tn_align", "vsc_align_forward_sim", "vsc_tn_set_timestamps", "vsc_tn_match_rows",
+    "vsc_tn_align", "vsc_align_forward_sim", "vsc_tn_set_timestamps", "vsc_tn_match_rows", "vsc_match_metric",
     "vsc_index_profile", "vsc_index_profile_read", "vsc_index_profile_read_class", "vsc_index_search_stats",
     "vsc_aux_profile", "vsc_aux_profile_read", "vsc_bias_act_bf16", "vsc_gemm_bias_act_bf16", "vsc_pool3x3s2_bias_relu_bf16", "vsc_conv_bias_act_bf16",
     "vsc_vit_attention_bf16", "vsc_layernorm_bf16", "vsc_vit_tokens_bf16", "vsc_vit_cdpool_bf16",
@@ -209,6 +210,7 @@ def lib():
         L.vsc_align_forward_sim.argtypes = [vp, vp, vp, vp, i64, ctypes.POINTER(AlignParams), vp, vp, vp, vp, i32]
         L.vsc_tn_set_timestamps.argtypes = [vp, vp, vp, i32]
         L.vsc_tn_match_rows.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp, i64, i32, pi64]
+        L.vsc_match_metric.argtypes = [vp, vp, i64, vp, i64, i32, vp, vp, vp, i64, i32, i64, vp, vp, i64, pi64, vp, vp, i32]
         L.vsc_index_profile.argtypes = [vp, i32]
         L.vsc_index_profile_read.argtypes = [vp, ctypes.POINTER(ctypes.c_double), pi64,
                                              ctypes.POINTER(ctypes.c_double), i32]

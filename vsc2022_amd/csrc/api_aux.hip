@@ -1,4 +1,4 @@
-// C ABI of libvscmi.so, part 4: the entry points that own no index handle (vsc_pair_max, vsc_row_normalize) and the
+// C ABI of libvscmi.so, part 4: the entry points that own no index handle (vsc_pair_max, vsc_row_normalize, vsc_match_metric) and the
 // Temporal-Network localisation contexts (vsc_tn_*), the DTW / DP aligners on them (vsc_tn_align, vsc_align_forward_sim)
 // and the match-rows stage behind both (vsc_tn_set_timestamps, vsc_tn_match_rows).
 #include "api_internal.h"
@@ -11,6 +11,8 @@ struct DeviceCtx {
     hipStream_t stream = nullptr;      // own_stream, or the caller's (vsc_set_aux_stream)
     hipStream_t own_stream = nullptr;
     Workspace ws;
+    MetricScratch metric;  // vsc_match_metric
+    DevBuf metric_in[6];   // ... and its host-memory tables
     std::mutex mu;
 };
 static DeviceCtx* device_ctx(int device) {
@@ -298,6 +300,44 @@ int vsc_row_normalize(const float* x, int64_t n, int dim, int x_mem, float* out,
         VSC_HIP(hipMemcpyAsync(out, dout, (size_t)n * dim * 4, hipMemcpyDeviceToHost, c->stream));
     VSC_HIP(hipStreamSynchronize(c->stream));
     return VSC_OK;
+}
+
+// Segment AP of the matching track (include/vscmi.h): uploads, then metric.hip's match_metric_device
+int vsc_match_metric(const int32_t* gt_pair, const double* gt_times, int64_t n_gt, const int32_t* gt_first, int64_t n_gt_pairs,
+                     int gt_mem, const int32_t* pred_pair, const double* pred_score, const double* pred_times, int64_t n_pred,
+                     int pred_mem, int64_t n_pairs, double* out_score, double* out_sums, int64_t cap, int64_t* n_groups,
+                     double* gt_len, int64_t* stats, int device) {
+    if (!n_groups || !gt_len || n_gt < 0 || n_pred < 0 || n_pairs < 0 || n_gt_pairs < 0 || n_gt_pairs > n_pairs || cap < 0 ||
+        (n_gt > 0 && (!gt_pair || !gt_times)) || (n_pred > 0 && (!pred_pair || !pred_score || !pred_times)) ||
+        (cap > 0 && (!out_score || !out_sums))) {
+        set_error("vsc_match_metric: invalid argument");
+        return VSC_ERR_INVALID;
+    }
+    *n_groups = 0;
+    gt_len[0] = gt_len[1] = 0.0;
+    if (stats) memset(stats, 0, 8 * sizeof(int64_t));
+    VSC_TRY(check_device(device));
+    VSC_HIP(hipSetDevice(device));
+    DeviceCtx* c = device_ctx(device);
+    if (!c) {
+        set_error("vsc_match_metric: cannot create device context");
+        return VSC_ERR_HIP;
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    const void *dgp, *dgt, *dgf = nullptr, *dpp, *dps, *dpt;
+    VSC_TRY(to_device(gt_pair, (size_t)n_gt * 4, gt_mem, c->metric_in[0], &dgp, c->stream));
+    VSC_TRY(to_device(gt_times, (size_t)n_gt * 32, gt_mem, c->metric_in[1], &dgt, c->stream));
+    if (gt_first) VSC_TRY(to_device(gt_first, (size_t)n_gt_pairs * 4, gt_mem, c->metric_in[2], &dgf, c->stream));
+    VSC_TRY(to_device(pred_pair, (size_t)n_pred * 4, pred_mem, c->metric_in[3], &dpp, c->stream));
+    VSC_TRY(to_device(pred_score, (size_t)n_pred * 8, pred_mem, c->metric_in[4], &dps, c->stream));
+    VSC_TRY(to_device(pred_times, (size_t)n_pred * 32, pred_mem, c->metric_in[5], &dpt, c->stream));
+    MetricIn in{(const int32_t*)dgp, (const double*)dgt, n_gt, (const int32_t*)dgf, n_gt_pairs,
+                (const int32_t*)dpp, (const double*)dps, (const double*)dpt, n_pred, n_pairs};
+    MetricOut out{out_score, out_sums, cap, 0, gt_len, {0, 0, 0, 0, 0, 0, 0, 0}};
+    const int rc = match_metric_device(in, c->metric, out, c->stream);
+    *n_groups = out.n_groups;
+    if (stats) for (int k = 0; k < 8; ++k) stats[k] = out.stats[k];
+    return rc;
 }
 
 }  // extern "C"

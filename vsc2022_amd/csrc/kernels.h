@@ -182,6 +182,25 @@ struct MatchRowsArgs {
     int64_t* ctl;       // [0] rows of the batch, [1] error word (bit 0 box count, bit 1 pair ordinal, bit 2 corner)
     int32_t* out_pair; int32_t* out_box; float* out_score; double* out_times;  // out_box may be nullptr
 };
+// Segment AP (metric.hip): the tables of vsc_match_metric in device memory -> the group-end sums in host memory
+// (kept with the device context for the life of the process, as its Workspace is: ~100 B per prediction row of the largest
+// call so far, 40 MB at 400 000 rows)
+struct MetricScratch {
+    DevBuf buf[24];
+};
+struct MetricIn {
+    const int32_t* gt_pair; const double* gt_times; int64_t n_gt;
+    const int32_t* gt_first; int64_t n_gt_pairs;  // the ground truth's pairs in first-appearance order (nullptr: 0, 1, 2, ...)
+    const int32_t* pred_pair; const double* pred_score; const double* pred_times; int64_t n_pred;
+    int64_t n_pairs;
+};
+struct MetricOut {
+    double* scores; double* sums; int64_t cap;  // host: [cap], [cap][4]
+    int64_t n_groups;
+    double* gt_len;    // host [2]
+    int64_t stats[8];  // pairs on the LDS route, pairs on the HBM route, rows, groups; microseconds of the sorts, the pair
+                       // kernels and the ordered sums (0 unless vsc_aux_profile is on); 0
+};
 // The working state of one pair, all of it in LDS: byte offsets into the workgroup's dynamic array and their sum.  The
 // kernel carves by the pair's own shape; a launch asks for the largest `total` among its pairs.
 //   both: tile   the similarity matrix, fp32 [lq][lr] (not in forward_sim mode: the caller's matrix is read in place)
@@ -282,6 +301,7 @@ int launch_align_pairs(const AlignArgs&, size_t, hipStream_t);
 int64_t match_rows_tiles(int64_t n_pairs);
 int launch_match_rows_scan(const MatchRowsArgs&, hipStream_t);
 int launch_match_rows_emit(const MatchRowsArgs&, hipStream_t);
+int match_metric_device(const MetricIn&, MetricScratch&, MetricOut&, hipStream_t);
 // SQfp16 codec (codec_f16.hip)
 int launch_encode_rows(const void*, bool, int64_t, int, _Float16*, float*, int64_t, int64_t, int, bool, int*, hipStream_t);
 int launch_decode_rows(const _Float16*, int, bool, int64_t, int64_t, int64_t, float*, int, bool, hipStream_t);

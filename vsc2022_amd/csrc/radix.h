@@ -47,7 +47,8 @@ __global__ __launch_bounds__(256) void radix_hist_kernel(const K* __restrict__ k
 }
 
 // one workgroup per digit row: exclusive scan of its ntiles counts in place; row total -> totals[digit]
-__global__ __launch_bounds__(256) void radix_scan_rows_kernel(unsigned* __restrict__ hist, int ntiles,
+// (static, as the next one: the header is included by more than one translation unit)
+static __global__ __launch_bounds__(256) void radix_scan_rows_kernel(unsigned* __restrict__ hist, int ntiles,
                                                               unsigned* __restrict__ totals) {
     __shared__ unsigned part[256];
     unsigned* row = hist + (int64_t)blockIdx.x * ntiles;
@@ -73,7 +74,7 @@ __global__ __launch_bounds__(256) void radix_scan_rows_kernel(unsigned* __restri
     if (threadIdx.x == 255) totals[blockIdx.x] = part[255];
 }
 
-__global__ __launch_bounds__(256) void radix_scan_totals_kernel(unsigned* __restrict__ totals) {
+static __global__ __launch_bounds__(256) void radix_scan_totals_kernel(unsigned* __restrict__ totals) {
     __shared__ unsigned part[256];
     part[threadIdx.x] = totals[threadIdx.x];
     __syncthreads();

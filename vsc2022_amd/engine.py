@@ -479,6 +479,45 @@ class DeviceMatcher:
                           times[:, 2].astype(r_t), times[:, 3].astype(r_t), res.row_cand.cpu().numpy(),
                           res.row_boxes.cpu().numpy())
 
+    def segment_ap(self, res: MatchResult, gt, q_ids, r_ids):
+        """Segment AP (vsc.metrics.match_metric) of a result of `match(rows=True)` against the ground-truth MatchTable
+        `gt`, scored while the rows are still in HBM: equals `match_metric_table(gt, self.match_table(res, q_ids, r_ids))`
+        bit for bit.  A row's pair is its candidate (`res.row_cand`: candidates are unique pairs); the few ground-truth
+        rows are mapped to candidate indices by id on the host, pairs absent from the candidates get fresh ordinals."""
+        import pandas
+
+        from vsc2022_amd.vsc import metrics as M
+
+        if res.row_cand is None:
+            raise ValueError("segment_ap needs a result of match(rows=True)")
+        n_rows, n_cand = int(res.row_cand.numel()), int(res.cand_q.numel())
+        if n_rows == 0:
+            return M.segment_ap_tail(np.zeros(0), np.zeros((0, 4)), np.zeros(2))
+        n_r = max(len(r_ids), 1)
+        gq = pandas.Index(M.MatchTable._ids(q_ids)).get_indexer(gt.query_id).astype(np.int64)
+        gr = pandas.Index(M.MatchTable._ids(r_ids)).get_indexer(gt.ref_id).astype(np.int64)
+        cand_key = res.cand_q.cpu().numpy().astype(np.int64) * n_r + res.cand_r.cpu().numpy().astype(np.int64)
+        known = (gq >= 0) & (gr >= 0)
+        gt_pair = np.full(len(gt), -1, dtype=np.int64)
+        gt_pair[known] = pandas.Index(cand_key).get_indexer(gq[known] * n_r + gr[known])
+        fresh = np.flatnonzero(gt_pair < 0)
+        n_pairs = n_cand
+        if len(fresh):
+            q_code = pandas.factorize(gt.query_id[fresh].astype(object))[0].astype(np.int64)
+            r_code, r_names = pandas.factorize(gt.ref_id[fresh].astype(object))
+            code, names = pandas.factorize(q_code * max(len(r_names), 1) + r_code)
+            gt_pair[fresh] = n_cand + code
+            n_pairs += len(names)
+        gt_first = pandas.unique(gt_pair).astype(np.int32)
+        # (the tensors the library reads are made BEFORE the ordering point: torch's casts are queued work like any other)
+        row_pair = res.row_cand.to(torch.int32).contiguous()
+        row_score, row_times = res.row_score.to(torch.float64).contiguous(), res.row_times.contiguous()
+        self._order()
+        scores, sums, gt_len, stats = M.device_group_sums(gt_pair.astype(np.int32), M._times64(gt), gt_first, len(gt_first),
+                                                          row_pair, row_score, row_times, n_pairs, self.tdev.index)
+        self.last_metric_stats = stats
+        return M.segment_ap_tail(scores, sums, gt_len)
+
     # ---- the query-sharded search
     def _rows_above(self, rows: torch.Tensor, radius: float, budget: int, index: Optional[FlatIndex] = None):
         """EVERY pair of the query rows `rows` with score > radius (strict): (i relative to rows, j, s), sorted by (score
