@@ -98,6 +98,18 @@ int vsc_device_count(void);
  *   VSC_I8P_PAIR=0 / 2        never / always (dims <= 512) use work items of two 128-row panels (256 x 32 wave tiles;
  *                             default 1: where a launch is large enough)
  *   VSC_I8_SCREEN=1           fp16 screen between the int8 pre-filter and the exact stage (measured neutral: off)
+ *   VSC_DEFER=0|1|2           deferred rescoring in vsc_index_global_topk: pre-filtered batches leave the exact score of
+ *                             a pair uncomputed when it is proven to exceed the radius and to lie at or below a floor
+ *                             under which the next re-threshold event is expected to cut; the event then drops the
+ *                             pair unscored (or, where the guess was too high, scores it first).  Results, order, radius
+ *                             and events are those of 0 (off).  1 (default): the batches an event is expected to follow;
+ *                             2: every pre-filtered batch (tests).  VSC_DEFER_I8=0: fp16 batches only (int8 batches defer
+ *                             through the fp16 screen).  VSC_DEFER_MARGIN=<m> (0.05): the floor is the score of rank
+ *                             (K + 1) rows seen / rows at the expected event x (1 + m) among the kept hits.  Off in seeded
+ *                             searches, with VSC_SORT_HITS=0, a caller-sized hit buffer, VSC_RESCORE_SORT=0, the k-NN and
+ *                             vsc_index_range_search.  Read-only options of the last search: "deferred" (pairs),
+ *                             "defer_forced" (pairs scored after all), "defer_events_ok", "defer_events_forced",
+ *                             "n_rethreshold"
  *   VSC_KNN_STEP=n            query rows per launch of a k-NN threshold pass (default: 32768, doubled until rows x range
  *                             reaches VSC_KNN_STEP_WORK (64) x 32768 x 196608 or VSC_KNN_STEP_MAX (262144) rows)
  *   VSC_I8_KNN=0              k-NN threshold passes on the fp16 kernel

@@ -1,0 +1,194 @@
+"""Deferred rescoring (option "defer", csrc/api_search.hip "the deferred set"): a search that leaves exact scores
+uncomputed for pairs the next re-threshold event will drop must return what `defer = 0` and the CPU oracle return --
+rows, refs, score bits, order, final radius and the number of events -- on every route and whatever the floor guessed.
+All comparisons are on integers and fp32 bit patterns.
+
+Modes: 0 off, 1 the pre-filtered batches an event is expected to follow (default), 2 every pre-filtered batch.  fp16
+batches mark their candidates in the pre-filter kernel, int8 batches tell theirs apart in the fp16 screen."""
+import functools
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+ROUTES = {"fp16": {"prefilter": 2, "i8": 0}, "int8": {"prefilter": 2, "i8": 2}, "default": {}}
+STATS = ("deferred", "defer_forced", "defer_events_ok", "defer_events_forced")
+
+
+def unit(rng, n, d):
+    x = rng.standard_normal((n, d)).astype(np.float32)
+    return x / np.linalg.norm(x, axis=1, keepdims=True)
+
+
+def bits(x):
+    return np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+
+
+@functools.lru_cache(maxsize=None)
+def data(name):
+    """The inputs of a case, built once and never modified."""
+    if name == "d512":   # several re-thresholds: 32 + 64 + 128 + 76 rows
+        rng = np.random.default_rng(0)
+        q, r = unit(rng, 300, 512), unit(rng, 900, 512)
+    elif name == "d16":
+        rng = np.random.default_rng(5)
+        q, r = unit(rng, 2100, 16), unit(rng, 257, 16)
+    elif name == "d64":
+        rng = np.random.default_rng(1)
+        q, r = unit(rng, 1000, 64), unit(rng, 1000, 64)
+    elif name in ("ties", "ties8"):  # the data of test_global_topk_with_exact_ties
+        rng = np.random.default_rng(7)
+        q, r = np.repeat(unit(rng, 60, 64), 5, axis=0), np.repeat(unit(rng, 80, 64), 4, axis=0)
+        if name == "ties8":
+            q = (np.round(unit(rng, 200, 8) * 2) / 2).astype(np.float32)
+            r = (np.round(unit(rng, 300, 8) * 2) / 2).astype(np.float32)
+    elif name == "carry":  # rows 96..223 score low: the boundary at row 224 passes without an event
+        rng = np.random.default_rng(21)
+        q, r = unit(rng, 520, 32), unit(rng, 400, 32)
+        q[96:224] *= np.float32(0.6)
+    elif name == "l2":
+        rng = np.random.default_rng(11)
+        q, r = unit(rng, 150, 24), unit(rng, 170, 24)
+    else:
+        raise KeyError(name)
+    q.setflags(write=False)
+    r.setflags(write=False)
+    return q, r
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name, K, metric=0):
+    import oracle as orc
+
+    q, r = data(name)
+    return orc.global_threshold_search(q, r, K, metric, return_info=True)
+
+
+def boundaries(name, K):
+    """The schedule replayed on the oracle's scores: [(rows seen, kept before the event's test, event?)]."""
+    import oracle as orc
+
+    q, r = data(name)
+    S = orc.scores(q, r)
+    radius, kept, out, bs, i0 = np.float32(-1e10), np.empty(0, np.float32), [], 32, 0
+    while i0 < len(q):
+        i1 = min(len(q), i0 + bs)
+        new = S[i0:i1].ravel()
+        kept = np.concatenate([kept, new[new > radius]])
+        n, event = len(kept), len(kept) > 2 * K
+        if event:
+            radius = np.sort(kept)[::-1][K]
+            kept = kept[kept > radius]
+        out.append((i1, n, event))
+        if bs < 20000:
+            bs *= 2
+        i0 = i1
+    return out
+
+
+def search(name, K, route, defer, margin=None, metric=0):
+    from vsc2022_amd.vsc.index import FlatIndex
+
+    q, r = data(name)
+    opts = dict(ROUTES[route], defer=defer)
+    if margin is not None:
+        opts["defer_margin"] = margin
+    idx = FlatIndex(q.shape[1], metric, options=opts)
+    idx.add(r)
+    i, j, s, radius = idx.global_topk(q, K)
+    st = {k: int(idx.get_option(k)) for k in STATS}
+    st["n_rethreshold"] = int(idx.get_option("n_rethreshold"))
+    return (i, j, s, np.float32(radius)), st
+
+
+def same(a, b):
+    return (np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and np.array_equal(bits(a[2]), bits(b[2]))
+            and bits(a[3]) == bits(b[3]))
+
+
+def check(name, K, route, defer, margin=None, metric=0):
+    """The search with `defer` equals defer = 0 and the oracle; returns its statistics."""
+    got, st = search(name, K, route, defer, margin, metric)
+    off, st0 = search(name, K, route, 0, None, metric)
+    oi, oj, os_, info = reference(name, K, metric)
+    want = (oi, oj, os_, np.float32(info["radius"]))
+    assert same(off, want), (name, K, route, "defer = 0 differs from the oracle")
+    assert same(got, want), (name, K, route, defer, margin, st)
+    assert st["n_rethreshold"] == st0["n_rethreshold"] == info["n_rethreshold"], (st, st0, info)
+    assert all(st0[k] == 0 for k in STATS), st0
+    return st
+
+
+CASES = [("d512", 5000), ("d16", 9000), ("d64", 60000)]
+
+
+@pytest.mark.parametrize("route", list(ROUTES))
+@pytest.mark.parametrize("name,K", CASES)
+def test_forced_deferral_matches(gpu, orc, name, K, route):
+    st = check(name, K, route, 2)
+    if route != "default":  # (at these sizes the default route pre-filters few batches or none)
+        assert st["deferred"] > 0, st
+
+
+@pytest.mark.parametrize("route", ["fp16", "int8"])
+@pytest.mark.parametrize("name,K", CASES)
+def test_events_decided_with_d_left_out(gpu, orc, name, K, route):
+    """The default rule at margin 0.10: deferral only while an event can follow, every event is decided by the scored
+    hits alone, no pair of D is ever scored."""
+    st = check(name, K, route, 1, 0.10)
+    assert st["deferred"] > 0 and st["defer_events_ok"] >= 2, st
+    assert st["defer_forced"] == 0 and st["defer_events_forced"] == 0, st
+
+
+@pytest.mark.parametrize("route", ["fp16", "int8"])
+@pytest.mark.parametrize("name,K", CASES)
+def test_floor_guessed_too_high(gpu, orc, name, K, route):
+    """margin -0.5: the floor lies above the next radius, the event cannot be decided without D: D is re-scored."""
+    st = check(name, K, route, 2, -0.5)
+    assert st["defer_events_forced"] >= 1 and st["defer_forced"] > 0, st
+
+
+@pytest.mark.parametrize("route", ["fp16", "int8"])
+def test_d_outstanding_at_the_end(gpu, orc, route):
+    name, K = "d512", 5000
+    b = boundaries(name, K)
+    assert b[-1][0] == 300 and not b[-1][2] and b[-2][2], b  # the last event lies before the last batch
+    st = check(name, K, route, 2)
+    assert st["defer_events_forced"] == 0 and st["defer_forced"] > 0, st
+
+
+@pytest.mark.parametrize("route", list(ROUTES))
+def test_ties_on_radius_and_floor(gpu, orc, route):
+    """Repeated rows: tie groups of 20 and, with the rounded 8-d rows, of thousands sit on the radius and on the floor; a
+    group that straddles the floor is split between A and D and must come out whole."""
+    deferred = 0
+    for name, Ks in (("ties", (100, 777, 5000, 20000)), ("ties8", (50, 500, 5000))):
+        for K in Ks:
+            deferred += check(name, K, route, 2)["deferred"]
+            deferred += check(name, K, route, 2, -0.5)["deferred"]
+    if route != "default":
+        assert deferred > 0
+
+
+@pytest.mark.parametrize("route", ["fp16", "int8"])
+def test_d_carried_over_a_boundary_without_event(gpu, orc, route):
+    name, K = "carry", 4000
+    b = dict((rows, (kept, ev)) for rows, kept, ev in boundaries(name, K))
+    assert b[96][1] and not b[224][1] and b[224][0] <= 2 * K and b[480][1], b
+    st = check(name, K, route, 2)
+    # the events at rows 96 and 480 are decided without D; the one at 480 drops the pairs of two batches
+    assert st["deferred"] > 0 and st["defer_events_ok"] >= 2 and st["defer_events_forced"] == 0, st
+
+
+@pytest.mark.parametrize("K", [300, 4000])
+def test_l2_metric(gpu, orc, K):
+    """L2 indexes keep no pre-filter image: nothing is deferred, whatever the option says."""
+    for defer in (1, 2):
+        st = check("l2", K, "default", defer, metric=1)
+        assert all(st[k] == 0 for k in STATS), st
+
+
+@pytest.mark.parametrize("name,K", CASES + [("carry", 4000), ("ties", 777)])
+def test_default_mode_small_search(gpu, orc, name, K):
+    check(name, K, "default", 1)

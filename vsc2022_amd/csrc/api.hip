@@ -131,6 +131,7 @@ static const OptionName kOptions[] = {
     {"knn_s0min", "VSC_KNN_S0MIN"}, {"knn_ratio", "VSC_KNN_RATIO"}, {"knn_nchunk", "VSC_KNN_NCHUNK"}, {"knn_first_tile", "VSC_KNN_FIRST_TILE"},
     {"cand_budget", "VSC_CAND_BUDGET"}, {"debug_i8", "VSC_DEBUG_I8"}, {"debug_screen", "VSC_DEBUG_SCREEN"},
     {"topk_shortcut", "VSC_TOPK_SHORTCUT"}, {"topk_sample", "VSC_TOPK_SAMPLE"}, {"sort_hits", "VSC_SORT_HITS"}, {"density_hint", "VSC_DENSITY_HINT"},
+    {"defer", "VSC_DEFER"}, {"defer_margin", "VSC_DEFER_MARGIN"}, {"defer_i8", "VSC_DEFER_I8"},
 };
 
 // Options that decide which images of the reference rows are kept can only change while the index is empty.
@@ -208,6 +209,9 @@ static int apply_option(vsc_index* idx, const char* name, double v) {
     if (is("topk_sample")) { if (!(v >= 2.0)) goto bad; idx->topk_sample_rows = (int64_t)v; return VSC_OK; }
     if (is("sort_hits")) { idx->sort_hits = v != 0.0; return VSC_OK; }
     if (is("density_hint")) { if (!(v >= 0.0)) goto bad; idx->density_hint = v; return VSC_OK; }
+    if (is("defer")) { const int m = (int)v; if (m < 0 || m > 2) goto bad; idx->defer = m; return VSC_OK; }
+    if (is("defer_i8")) { idx->defer_i8 = v != 0.0; return VSC_OK; }
+    if (is("defer_margin")) { if (!(v > -1.0 && v < 100.0)) goto bad; idx->defer_margin = v; return VSC_OK; }
     set_error("vsc_index_set_option: unknown option '%s'", name);
     return VSC_ERR_INVALID;
 bad:
@@ -249,6 +253,16 @@ static int read_option(const vsc_index* idx, const char* name, double* out) {
     else if (is("topk_sample")) *out = (double)idx->topk_sample_rows;
     else if (is("sort_hits")) *out = idx->sort_hits;
     else if (is("density_hint")) *out = idx->density_hint;
+    else if (is("defer")) *out = idx->defer;
+    else if (is("defer_margin")) *out = idx->defer_margin;
+    else if (is("defer_i8")) *out = idx->defer_i8;
+    // (read-only, the last vsc_index_global_topk: pairs whose exact score was deferred, pairs of them re-scored after
+    // all, events decided with the deferred set left out, events that needed it re-scored first, events)
+    else if (is("deferred")) *out = (double)idx->stat_deferred;
+    else if (is("defer_forced")) *out = (double)idx->stat_defer_forced;
+    else if (is("defer_events_ok")) *out = (double)idx->stat_defer_events_ok;
+    else if (is("defer_events_forced")) *out = (double)idx->stat_defer_events_forced;
+    else if (is("n_rethreshold")) *out = (double)idx->stat_n_rethreshold;
     else if (is("last_topk_route")) *out = idx->last_topk_route;  // (read-only: what the last vsc_index_global_topk did)
     else if (is("i8_center")) *out = idx->i8_center;
     else if (is("i8_center_on")) *out = idx->i8_mu_on;        // (read-only: is the int8 reference image centred?)

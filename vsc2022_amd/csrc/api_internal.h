@@ -34,6 +34,7 @@ struct Workspace {
     DevBuf q8, pstat;       // int8 image + per-panel {1/s, E, N, s} of ONE launch's query rows (sim_i8p.hip)
     DevBuf cs[4], cstmp, csn;  // candidates of a launch compacted + sorted by reference row (keys, values, ping-pong)
     DevBuf tailfill;        // fill levels of the chunks of the candidate list's shared tail (cand_list.h)
+    DevBuf dd[2];           // the deferred set D of a search: (row, ref) of kept hits without a score yet (api_search.hip)
     DevBuf rt8c;            // the rows' largest |x| (second sort key of launches with per-row thresholds)
     DevBuf rt8d;            // centred reference image: x . mu and sum |x mu| of the launch's rows
     DevBuf rt8, rt8b;       // ... and its row thresholds in position order (rows sorted by threshold inside a launch);
@@ -55,6 +56,7 @@ struct Workspace {
         q8.release(); pstat.release(); rt8.release(); rt8b.release(); rt8c.release(); rt8d.release(); tailfill.release();
         for (auto& b : cs) b.release();
         cstmp.release(); csn.release();
+        for (auto& b : dd) b.release();
         for (auto& b : hA) b.release();
         for (auto& b : hB) b.release();
         ctl.release(); sort.release(); cnt.release();
@@ -142,6 +144,18 @@ struct vsc_index {
     int i8_group_shift = 9;      // VSC_I8_GROUP=<log2 rows>: radius searches with per-row thresholds order groups of 2^n rows by scale (0: off)
     bool rescore_by_ref = true;  // VSC_RESCORE_SORT=0: re-score the waves' segments as they are
     bool i8_screen = false;      // VSC_I8_SCREEN=1: fp16 screen between the int8 pre-filter and the exact stage
+    // Deferred rescoring (api_search.hip, "the deferred set").  VSC_DEFER: 0 off, 1 the pre-filtered batches of the schedule
+    // that an event is expected to follow (default), 2 every pre-filtered batch whatever the expectation (tests).
+    // VSC_DEFER_I8=0: only the fp16 batches defer, not the int8 ones (which defer through the fp16 screen).
+    // VSC_DEFER_MARGIN: the floor's rank is (K + 1) b / b_next (1 + margin)
+    int defer = 1;
+    bool defer_i8 = true;
+    double defer_margin = 0.05;
+    // the last search: pairs deferred, pairs of D re-scored after all, events decided with D left out, events that
+    // needed D re-scored first, re-threshold events
+    unsigned long long stat_deferred = 0, stat_defer_forced = 0, stat_defer_events_ok = 0, stat_defer_events_forced = 0;
+    unsigned long long stat_n_rethreshold = 0;
+    bool defer_now = false;  // (transient, set by the schedule around one batch: this batch's pre-filter and exact stage defer)
     bool knn_i8 = true;          // VSC_I8_KNN=0: k-NN passes on the fp16 kernel
     bool knn_two_level = true;   // VSC_KNN_LEVELS=1: one refinement level
     double knn_subset_factor = 300.0;  // VSC_KNN_SUBSET

@@ -88,6 +88,7 @@ static int prefilter_f16_panel(vsc_index* idx, const F16Batch& b, int64_t ccap, 
     f.c1 = fb.c1; f.c2 = fb.c2; f.c3 = fb.c3;
     f.radius = &idx->ws.ctl.as<SelectCtl>()->radius;
     f.row_thr = b.row_thr ? b.row_thr + b.i0 : nullptr;
+    f.floor = idx->defer_now && !b.row_thr ? &idx->ws.ctl.as<SelectCtl>()->floor : nullptr;
     VSC_TRY(cand_list_plan(idx, ccap, grid, cl));
     f.list = cl;
     VSC_TRY(prof_begin(idx, stop, 1));
@@ -207,21 +208,16 @@ static int prefilter_i8(vsc_index* idx, const F16Batch& b, int64_t ccap, CandLis
     return launch_sim_i8p(f, grid, idx->stream);
 }
 
-// Exact scores of a launch's candidates `cl`; those above the radius (at or above the row's threshold) join the kept
-// hits, at most `cap` of them.  `perm`: the list holds positions of a permuted int8 launch; `from_i8`: the candidates
-// may pass the fp16 screen first.
-static int exact_stage(vsc_index* idx, const F16Batch& b, int64_t cap, const CandList& cl, const int32_t* perm,
-                       const F16Bound& fb, bool from_i8) {
+// What every launch of the exact stage shares: the images, the kept-hit list behind the search's control block.
+static RescoreArgs rescore_args(vsc_index* idx, const float* qpacked, int64_t cap) {
     SelectCtl* ctl = idx->ws.ctl.as<SelectCtl>();
-    Workspace& ws = idx->ws;
-    const HitView kept = ws.hits_a();
+    const HitView kept = idx->ws.hits_a();
     RescoreArgs r;
-    r.Q = b.qpacked;
+    r.Q = qpacked;
     r.R = idx->ref.as<float>();
     r.dpad = idx->dpad;
-    r.list = cl;
-    r.perm = perm;
-    r.perm_i0 = (int)b.i0;
+    r.perm = nullptr;
+    r.perm_i0 = 0;
     r.n_cand_total = &ctl->n_cand_total;
     r.radius = &ctl->radius;
     r.out_i = kept.i;
@@ -229,14 +225,29 @@ static int exact_stage(vsc_index* idx, const F16Batch& b, int64_t cap, const Can
     r.out_s = kept.s;
     r.counter = &ctl->n;
     r.cap = cap;
-    r.row_thr = b.row_thr;
-    r.j0 = (int)b.nr_begin;
+    r.row_thr = nullptr;
     if (sq16(idx)) {  // the reference rows come from the fp16 store (rescore.hip: rescore_list<SRC>)
         r.R = nullptr;
         r.Rh = idx->refh.as<_Float16>();
         r.dpadh = idx->dpadh;
         r.rsrc = idx->frag ? 2 : 1;
     }
+    return r;
+}
+
+// Exact scores of a launch's candidates `cl`; those above the radius (at or above the row's threshold) join the kept
+// hits, at most `cap` of them.  `perm`: the list holds positions of a permuted int8 launch; `from_i8`: the candidates
+// may pass the fp16 screen first.
+static int exact_stage(vsc_index* idx, const F16Batch& b, int64_t cap, const CandList& cl, const int32_t* perm,
+                       const F16Bound& fb, bool from_i8) {
+    SelectCtl* ctl = idx->ws.ctl.as<SelectCtl>();
+    Workspace& ws = idx->ws;
+    RescoreArgs r = rescore_args(idx, b.qpacked, cap);
+    r.list = cl;
+    r.perm = perm;
+    r.perm_i0 = (int)b.i0;
+    r.row_thr = b.row_thr;
+    r.j0 = (int)b.nr_begin;
     // The candidates are compacted out of the waves' segments, sorted by reference row and re-scored as one dense
     // list (rescore.hip, "candidates ordered by reference row"): 74 -> 54 ms per bench step, k-NN k = 20 140 ->
     // 100 ms.  It needs the candidate count on the host (buffer sizes, grid of the sort): one stream sync per
@@ -257,7 +268,26 @@ static int exact_stage(vsc_index* idx, const F16Batch& b, int64_t cap, const Can
     for (auto& buf : ws.cs)
         if (buf.bytes < (size_t)(n_c + 1) * sizeof(uint32_t)) VSC_TRY(buf.reserve(cap_e * sizeof(uint32_t)));
     uint32_t* cs[4] = {ws.cs[0].as<uint32_t>(), ws.cs[1].as<uint32_t>(), ws.cs[2].as<uint32_t>(), ws.cs[3].as<uint32_t>()};
+    // Deferred rescoring: this batch runs with a floor.  The deferred set D is as large as the kept-hit list (its pairs
+    // are kept hits); an fp16 launch has marked the pairs that go there (cand_compact moves them, and the dense list's
+    // length is then read back: the one extra read of a deferring batch), an int8 launch's pairs are told apart by
+    // the fp16 screen below.
+    const bool defer = idx->defer_now && !b.row_thr;
+    if (defer) {
+        for (auto& buf : ws.dd) VSC_TRY(buf.reserve((size_t)cap * sizeof(int32_t)));
+        if (!from_i8) {
+            r.d_i = ws.dd[0].as<int32_t>();
+            r.d_j = ws.dd[1].as<int32_t>();
+            r.d_count = &ctl->n_d;
+            r.d_total = &ctl->n_deferred;
+            r.d_cap = cap;
+        }
+    }
     VSC_TRY(launch_cand_compact(r, n_chunks_max, cs[0], cs[2], csn, idx->stream));
+    if (r.d_i) {
+        VSC_HIP(hipMemcpyAsync(&n_c, csn, sizeof(n_c), hipMemcpyDeviceToHost, idx->stream));
+        VSC_HIP(hipStreamSynchronize(idx->stream));
+    }
     const uint32_t *sj = nullptr, *si = nullptr;
     VSC_TRY(sort_candidates_by_ref(cs[0], cs[1], cs[2], cs[3], (int64_t)n_c, b.nr_end, ws.cstmp, &sj, &si, idx->stream));
     // VSC_I8_SCREEN=1: int8 launches pass an fp16 screen first (rescore.hip: f16_screen_kernel).  Measured
@@ -265,9 +295,19 @@ static int exact_stage(vsc_index* idx, const F16Batch& b, int64_t cap, const Can
     // step), the screen moves half the bytes per pair (23.8 ms) and the exact stage then costs 35.6 instead of
     // 59.8 ms -- both stages gather one query row per pair from the Infinity Cache at ~6 TB/s, which is the
     // bound (profiles/r03_prefilter_attribution.md).  Kept because it pays once the survivor share drops
-    // (descriptors with outlier coordinates widen the int8 bound, not the fp16 one).
-    if (!(from_i8 && idx->i8_screen && n_c > 0)) return launch_rescore_dense(r, sj, si, (long long)n_c, idx->stream);
+    // (descriptors with outlier coordinates widen the int8 bound, not the fp16 one) -- and in a batch that defers: there
+    // the screen also takes out the pairs whose exact score can wait (configs[3]: the step gains 20 ms by it,
+    // profiles/deferred_rescoring.md).
+    if (!(from_i8 && (idx->i8_screen || defer) && n_c > 0)) return launch_rescore_dense(r, sj, si, (long long)n_c, idx->stream);
     ScreenArgs sa;
+    if (defer) {
+        sa.floor = &ctl->floor;
+        sa.d_i = ws.dd[0].as<int32_t>();
+        sa.d_j = ws.dd[1].as<int32_t>();
+        sa.d_count = &ctl->n_d;
+        sa.d_total = &ctl->n_deferred;
+        sa.d_cap = cap;
+    }
     sa.Qh = ws.qh.as<_Float16>();
     sa.qn = ws.qn.as<float>();
     sa.Rh = idx->refh.as<_Float16>();
@@ -386,6 +426,115 @@ static int enqueue_batch(vsc_index* idx, const float* qpacked, int64_t i0, int64
     return VSC_OK;
 }
 
+// ---- the deferred set
+// range_search_max_results searches every batch at the radius of the LAST event, far below the one the next event will
+// set: about half of a batch's new hits are dropped again by that event.  Their exact scores are never looked at -- the
+// event only needs to know that they exist (the predicate kept > 2K) and that they lie at or below the new radius.  So
+// the kept set is held in two parts: A, the hit buffer with exact scores, and D, (row, ref) pairs whose exact score is
+// PROVEN (by the pre-filter's score and error bound) to lie in (radius, floor] and has not been computed.  The floor is a
+// guess of where the next radius will land: the score of rank (K + 1) b / b_next (1 + margin) among the kept hits of the
+// b rows seen so far, b_next = the boundary at which the predicate is expected to pass.
+//   event (select.hip, PICK_TRIAL): predicate n_A + n_D > 2K; v = (K+1)-th best of A alone.  v >= floor: every pair of D
+//     is <= floor <= v, so v is the (K+1)-th best of A and D together and D falls to the strict re-filter -- exactly the
+//     reference's step, with D never scored.  Else D is re-scored into A first (force_deferred) and the ordinary round
+//     runs: a wrong guess costs D's own re-scoring and one more selection, never a restart.
+//   no event: D stays outstanding (the radius has not moved, so its proof holds); the end of the search re-scores it.
+// Results, order, radius and the number of events are those of defer = 0 whatever the floor is.
+
+// Re-score the n_d pairs of D into the kept hits (sorted by reference row, the exact stage's dense form).  Every one of
+// them must pass score > radius: anything else means a pair was deferred without proof.
+static int force_deferred(vsc_index* idx, const float* qpacked, int64_t cap, unsigned long long n_d, unsigned long long n_before) {
+    SelectCtl* ctl = idx->ws.ctl.as<SelectCtl>();
+    Workspace& ws = idx->ws;
+    if (n_d == 0) return launch_defer_reset(ctl, idx->stream);
+    hipEvent_t stop;
+    VSC_TRY(prof_begin(idx, &stop, 2));
+    const size_t cap_e = (size_t)(n_d + n_d / 4 + 4096);
+    for (auto& buf : ws.cs)
+        if (buf.bytes < (size_t)(n_d + 1) * sizeof(uint32_t)) VSC_TRY(buf.reserve(cap_e * sizeof(uint32_t)));
+    uint32_t* cs[4] = {ws.cs[0].as<uint32_t>(), ws.cs[1].as<uint32_t>(), ws.cs[2].as<uint32_t>(), ws.cs[3].as<uint32_t>()};
+    VSC_HIP(hipMemcpyAsync(cs[0], ws.dd[1].p, (size_t)n_d * 4, hipMemcpyDeviceToDevice, idx->stream));
+    VSC_HIP(hipMemcpyAsync(cs[2], ws.dd[0].p, (size_t)n_d * 4, hipMemcpyDeviceToDevice, idx->stream));
+    const uint32_t *sj = nullptr, *si = nullptr;
+    VSC_TRY(sort_candidates_by_ref(cs[0], cs[1], cs[2], cs[3], (int64_t)n_d, idx->ntotal, ws.cstmp, &sj, &si, idx->stream));
+    RescoreArgs r = rescore_args(idx, qpacked, cap);
+    r.list = CandList{};  // (a dense list: only the overflow word and the tail counter are looked at)
+    VSC_TRY(ws.csn.reserve(3 * sizeof(unsigned long long)));
+    r.n_cand_total = ws.csn.as<unsigned long long>() + 1;  // (these pairs were counted as candidates when they were deferred)
+    r.list.overflow = &ctl->overflow;
+    r.list.tail_count = &ctl->n_tail;
+    VSC_TRY(launch_rescore_dense(r, sj, si, (long long)n_d, idx->stream));
+    VSC_TRY(launch_defer_reset(ctl, idx->stream));
+    VSC_TRY(prof_end(idx, stop, 0.0, 2));
+    SelectCtl h;
+    VSC_HIP(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, idx->stream));
+    VSC_HIP(hipStreamSynchronize(idx->stream));
+    if (!h.overflow && h.n != n_before + n_d) {
+        set_error("global_topk: %llu of %llu deferred pairs did not pass the radius when they were re-scored",
+                  n_before + n_d - h.n, n_d);
+        return VSC_ERR_INVALID;
+    }
+    idx->stat_defer_forced += n_d;
+    return VSC_OK;
+}
+
+// The floor for the batches from row b on (batch [b, i1) of `bs` rows comes next), or none.  n_a kept hits over b rows:
+// about n_a e / b at boundary e, so the predicate is expected to pass at the first boundary with n_a e > 2K b.
+static int choose_floor(vsc_index* idx, int64_t K, int64_t nq, int64_t b, int64_t i1, int64_t bs, bool* chosen, bool* no_event_left) {
+    SelectCtl* ctl = idx->ws.ctl.as<SelectCtl>();
+    const bool forced = idx->defer == 2;
+    *chosen = false;
+    SelectCtl h;
+    VSC_HIP(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, idx->stream));
+    VSC_HIP(hipStreamSynchronize(idx->stream));
+    if (h.overflow || h.n == 0 || b <= 0) return VSC_OK;
+    int64_t b_next = -1;
+    for (int64_t e = i1, sb = bs;;) {
+        if ((double)e * (double)h.n > 2.0 * (double)K * (double)b) { b_next = e; break; }
+        if (e >= nq) break;
+        if (sb < 20000) sb *= 2;
+        e = std::min(nq, e + sb);
+    }
+    if (b_next < 0) {
+        // no event can follow: deferring would only add D's re-scoring at the end (and the later batches need not ask)
+        if (!forced) { *no_event_left = true; return VSC_OK; }
+        b_next = 2 * b;
+    }
+    const double m = std::ceil(((double)K + 1.0) * ((double)b / (double)b_next) * (1.0 + idx->defer_margin));
+    if ((!(m >= 1.0) || m > (double)h.n) && !forced) return VSC_OK;
+    const unsigned long long rank = (unsigned long long)std::min(std::max(m, 1.0), (double)h.n) - 1ull;
+    hipEvent_t stop;
+    VSC_TRY(prof_begin(idx, &stop, 3));
+    VSC_TRY(enqueue_floor_select(ctl, idx->ws.hits_a().s, rank, idx->stream));
+    VSC_TRY(prof_end(idx, stop, 0.0, 3));
+    *chosen = true;
+    return VSC_OK;
+}
+
+// The batch boundary while a floor is set.  *open stays true when no event took place (D is carried on).
+static int deferred_event(vsc_index* idx, const float* qpacked, int64_t K, int64_t cap, bool* open) {
+    SelectCtl* ctl = idx->ws.ctl.as<SelectCtl>();
+    hipEvent_t stop;
+    VSC_TRY(prof_begin(idx, &stop, 3));
+    VSC_TRY(enqueue_rethreshold_deferred(ctl, idx->ws.hits_a(), idx->ws.hits_b(), (unsigned long long)K, idx->stream));
+    VSC_TRY(prof_end(idx, stop, 0.0, 3));
+    SelectCtl h;
+    VSC_HIP(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, idx->stream));
+    VSC_HIP(hipStreamSynchronize(idx->stream));
+    if (h.overflow) { *open = false; return VSC_OK; }  // (the schedule is rerun with larger buffers)
+    if (h.need_force) {
+        VSC_TRY(force_deferred(idx, qpacked, cap, h.n_d, h.n));
+        idx->stat_defer_events_forced += 1;
+        VSC_TRY(prof_begin(idx, &stop, 3));
+        VSC_TRY(enqueue_rethreshold(ctl, idx->ws.hits_a(), idx->ws.hits_b(), (unsigned long long)K, idx->stream));
+        VSC_TRY(prof_end(idx, stop, 0.0, 3));
+        *open = false;
+    } else if (!(h.floor < INFINITY)) {
+        *open = false;  // the event took place with D left out (or no floor could be chosen)
+    }
+    return VSC_OK;
+}
+
 int init_ctl(vsc_index* idx, float radius_score_space) {
     // (a one-workgroup kernel instead of a host-staged copy + synchronisation: the sharded schedule calls the seeded
     // search once per batch and rank, and every host round trip is ~40 us of idle GPU there -- profiles/r06_rank_work.md)
@@ -419,8 +568,14 @@ static int global_topk_impl(vsc_index_t* idx, const float* q, int64_t nq, int q_
     cap = std::min<int64_t>(cap, cap_max);
     SelectCtl h;
     bool allow_i8 = i8_usable(idx);
+    // deferred rescoring ("the deferred set" above): the reference's own schedule only -- a seeded search has no event to
+    // wait for, an unsorted result (the sharded schedule) and a caller-sized hit buffer keep their exact buffer use
+    const bool can_defer = idx->defer > 0 && !seeded && ip && idx->sort_hits && idx->hit_cap_user <= 0 && idx->rescore_by_ref && K >= 1;
     for (;;) {
         bool used_i8 = false;
+        bool d_open = false;  // a floor is set: the pre-filtered batches defer, D may hold pairs
+        bool no_event_left = false;
+        idx->stat_deferred = idx->stat_defer_forced = idx->stat_defer_events_ok = idx->stat_defer_events_forced = 0;
         VSC_TRY(ensure_hit_buffers(idx, cap));
         // initial radius -1e10 (IP) / +1e10 (L2) -> -1e10 in score space either way (vsc/index.py:146)
         VSC_TRY(init_ctl(idx, seeded ? (ip ? radius0 : -radius0) : -1e10f));
@@ -444,11 +599,21 @@ static int global_topk_impl(vsc_index_t* idx, const float* q, int64_t nq, int q_
             // second half (the bound of 8-bit rows is ~16x looser), the batch runs on int8
             const bool i8 = f16 && allow_i8 && (idx->i8_mode == 2 || dens < idx->i8_density);
             used_i8 |= i8;
-            VSC_TRY(enqueue_batch(idx, qp, i0, i1, cap, f16, i8));
+            // can this batch defer?  fp16: the panel kernel marks its candidates; int8 (option defer_i8): the fp16 screen
+            const bool defers = can_defer && !no_event_left && f16 && (i8 ? idx->defer_i8 : idx->frag);
+            if (defers && !d_open) VSC_TRY(choose_floor(idx, K, nq, i0, i1, bs, &d_open, &no_event_left));
+            idx->defer_now = defers && d_open;
+            const int rc_batch = enqueue_batch(idx, qp, i0, i1, cap, f16, i8);
+            idx->defer_now = false;
+            VSC_TRY(rc_batch);
             // The re-threshold round is predicated on the device (kept > 2K) and costs twelve launches even when it does
             // nothing.  Behind the LAST batch the control block is read back anyway: the round is enqueued there only
             // if that read says it has work to do (the one-batch calls of the sharded schedule almost never do).
-            if (i1 < nq) {
+            if (d_open) {
+                // (with D outstanding the round is the deferred form, and the host reads its outcome: the one sync a
+                // boundary behind a deferring batch adds)
+                VSC_TRY(deferred_event(idx, qp, K, cap, &d_open));
+            } else if (i1 < nq) {
                 hipEvent_t stop;
                 VSC_TRY(prof_begin(idx, &stop, 3));
                 VSC_TRY(enqueue_rethreshold(ctl, idx->ws.hits_a(), idx->ws.hits_b(), (unsigned long long)K, idx->stream));
@@ -459,6 +624,12 @@ static int global_topk_impl(vsc_index_t* idx, const float* q, int64_t nq, int q_
         }
         VSC_HIP(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, idx->stream));
         VSC_HIP(hipStreamSynchronize(idx->stream));
+        if (d_open && !h.overflow) {
+            // the end of the search with D outstanding (no event behind the last batches): its pairs are kept hits
+            VSC_TRY(force_deferred(idx, qp, cap, h.n_d, h.n));
+            VSC_HIP(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, idx->stream));
+            VSC_HIP(hipStreamSynchronize(idx->stream));
+        }
         if (!h.overflow && h.n > 2ull * (unsigned long long)K) {
             hipEvent_t stop;
             VSC_TRY(prof_begin(idx, &stop, 3));
@@ -467,6 +638,14 @@ static int global_topk_impl(vsc_index_t* idx, const float* q, int64_t nq, int q_
             VSC_HIP(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, idx->stream));
             VSC_HIP(hipStreamSynchronize(idx->stream));
         }
+        idx->stat_deferred = h.n_deferred;
+        idx->stat_defer_events_ok = h.ev_ok;
+        idx->stat_n_rethreshold = h.n_rethreshold;
+        if (idx->debug_i8 && can_defer)
+            fprintf(stderr, "[vscmi] deferred rescoring (defer %d, margin %g): %llu of %llu candidates deferred, %llu re-scored after all; "
+                    "%llu events decided without them, %llu needed them (%llu events)\n", idx->defer, idx->defer_margin,
+                    idx->stat_deferred, h.n_cand_total, idx->stat_defer_forced, idx->stat_defer_events_ok,
+                    idx->stat_defer_events_forced, idx->stat_n_rethreshold);
         VSC_TRY(prof_collect(idx));
         idx->stat_candidates = h.n_cand_total;
         if (!h.overflow) break;

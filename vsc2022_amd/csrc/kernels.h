@@ -61,6 +61,9 @@ struct SimF16PArgs {
     float c1, c2, c3;
     const float* radius; const float* row_thr;  // as in SimF16Args
     CandList list;
+    // deferred rescoring (radius searches only; nullptr or *floor = +inf: off): a candidate whose exact score is PROVEN to
+    // lie in (*radius, *floor] is stored with the top bit of its row set (DEFER_MARK) and goes to the deferred set
+    const float* floor = nullptr;
 };
 // panel-stationary INT8 pre-filter (sim_i8p.hip; dims <= 1024): the query side is the launch's own int8 image with one
 // scale per 128-row panel (quant_query_panels), the reference side the fragment-major int8 image + per-row meta of
@@ -91,6 +94,8 @@ struct SimI8PArgs {
     const float* radius; const float* row_thr;  // as in SimF16Args (row_thr indexed by POSITION inside the launch)
     CandList list;
 };
+// top bit of a candidate's row in a list written with SimF16PArgs::floor set: the pair is deferred, not re-scored
+constexpr uint32_t DEFER_MARK = 0x80000000u;
 struct RescoreArgs {
     const float* Q; const float* R; int dpad;  // packed fp32 images (exact arithmetic contract)
     CandList list;  // the pre-filter launch's candidates (cand_list.h); tail_count is reset to 0 after the pass
@@ -107,6 +112,10 @@ struct RescoreArgs {
     // SQfp16 codec: the reference rows are read from the fp16 store instead of R (rsrc: 0 = R, packed fp32; 1 = Rh in
     // natural layout; 2 = Rh fragment-major) and converted in registers; the chain is the same
     const _Float16* Rh = nullptr; int dpadh = 0; int rsrc = 0;
+    // the deferred set D (cand_compact: marked entries go here as (row, absolute ref) instead of the dense list);
+    // d_count = its fill level, d_total = pairs deferred so far (statistics).  More than d_cap sets bit 0 of *list.overflow
+    int32_t* d_i = nullptr; int32_t* d_j = nullptr; unsigned long long* d_count = nullptr; unsigned long long* d_total = nullptr;
+    long long d_cap = 0;
 };
 // fp16 screen of the int8 route's candidates (rescore.hip): the pair list sorted by reference row in, the pairs whose
 // fp16 score + error bound still reaches the threshold out
@@ -119,7 +128,12 @@ struct ScreenArgs {
     const uint32_t* sj; const uint32_t* si; long long n;
     uint32_t* out_j; uint32_t* out_i; unsigned long long* n_out;
     unsigned long long* n_cand_total;     // statistics: += n
-    const int* overflow;
+    int* overflow;
+    // deferred rescoring (floor != nullptr and *floor < +inf): a pair proven to lie in (*radius, *floor] joins the
+    // deferred set instead of the survivors (fields as in RescoreArgs)
+    const float* floor = nullptr;
+    int32_t* d_i = nullptr; int32_t* d_j = nullptr; unsigned long long* d_count = nullptr; unsigned long long* d_total = nullptr;
+    long long d_cap = 0;
 };
 struct SimKnnArgs {
     const float* Q; const float* R; int dpad; int nq; int nr; int tq; int tr; int nchunk; int k;
@@ -141,6 +155,13 @@ struct SelectCtl {
     unsigned long long n_rethreshold;
     unsigned long long n_cand_total;  // pre-filter candidates of the whole search (statistics)
     unsigned long long n_tail;        // fill level of the candidate list's shared tail (current batch)
+    // deferred rescoring (api_search.hip, "the deferred set"): pairs proven to lie in (radius, floor] wait in D, score-less
+    unsigned long long n_d;           // fill level of D
+    unsigned long long n_deferred;    // pairs that ever entered D (statistics)
+    float floor;                      // +inf: no floor chosen since the last event
+    int need_force;                   // the last event could not be decided with D left out: the host re-scores D
+    unsigned int ev_ok;               // events decided with a non-empty D left out (statistics)
+    unsigned int pad_;
 };
 struct TnPairArgs {
     const float* qfeat; const float* rfeat; const int64_t* q_off; const int64_t* r_off; int dpad;
@@ -288,6 +309,9 @@ int launch_matrix_thresh(const MatThreshArgs&, hipStream_t);
 int launch_matrix_knn(const MatKnnArgs&, hipStream_t);
 int set_thresh_kernel_attrs();
 int enqueue_rethreshold(SelectCtl*, HitView, HitView, unsigned long long, hipStream_t);
+int enqueue_rethreshold_deferred(SelectCtl*, HitView, HitView, unsigned long long, hipStream_t);
+int enqueue_floor_select(SelectCtl*, const float*, unsigned long long, hipStream_t);
+int launch_defer_reset(SelectCtl*, hipStream_t);
 int sort_hits_topk(ConstHitView, int64_t, int64_t, int64_t, int64_t, SortScratch&, HitView, int, int64_t*, hipStream_t);
 int sort_hits_rowcol(ConstHitView, int64_t, SortScratch&, HitView, int, hipStream_t);
 int pair_max_device(const int32_t*, const int32_t*, const float*, int64_t, const int32_t*, const int32_t*, int64_t, int64_t,

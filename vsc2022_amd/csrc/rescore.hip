@@ -207,6 +207,62 @@ __global__ __launch_bounds__(256) void cand_compact_kernel(RescoreArgs a, uint32
         cj = a.list.j + a.list.tail_base + (chunk << a.list.tail_shift);
     }
     if (n <= 0) return;
+    if (a.d_i) {
+        // a list written with a floor (deferred rescoring): entries with DEFER_MARK join the deferred set D -- (row,
+        // absolute ref), any order, no score --, the others the dense list.  Two walks over the (L2-resident) segment:
+        // the marked entries are counted first, so that the workgroup still takes one position per list
+        __shared__ unsigned int marked_sh, cur_sh[2];
+        __shared__ unsigned long long base_d_sh;
+        if (threadIdx.x == 0) { marked_sh = 0; cur_sh[0] = 0; cur_sh[1] = 0; }
+        __syncthreads();
+        unsigned int mine = 0;
+        for (int x = threadIdx.x; x < n; x += 256) mine += (uint32_t)ci[x] >> 31;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off);
+        if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&marked_sh, mine);
+        __syncthreads();
+        const unsigned int nm = marked_sh;
+        if (threadIdx.x == 0) {
+            base_sh = atomicAdd(n_out, (unsigned long long)(n - (int)nm));
+            base_d_sh = nm ? atomicAdd(a.d_count, (unsigned long long)nm) : 0ull;
+            if (nm) {
+                atomicAdd(a.d_total, (unsigned long long)nm);
+                atomicAdd(a.n_cand_total, (unsigned long long)nm);  // (the dense list's share is added by its re-scoring)
+            }
+        }
+        __syncthreads();
+        const unsigned long long base = base_sh, base_d = base_d_sh;
+        // (D is as large as the kept-hit list: a full D means the kept hits -- scored + deferred -- outgrew it)
+        const bool d_fits = (long long)(base_d + nm) <= a.d_cap;
+        if (!d_fits && threadIdx.x == 0) atomicOr(a.list.overflow, 1);
+        const int lane = threadIdx.x & 63;
+        for (int x0 = 0; x0 < n; x0 += 256) {
+            const int x = x0 + threadIdx.x;
+            const bool valid = x < n;
+            const uint32_t v = valid ? (uint32_t)ci[x] : 0u;
+            const bool marked = valid && (v & DEFER_MARK) != 0u, plain = valid && !marked;
+            const unsigned long long bm = __ballot(marked), bp = __ballot(plain);
+            unsigned int pm = 0, pp = 0;
+            if (lane == 0) {
+                if (bm) pm = atomicAdd(&cur_sh[1], (unsigned int)__popcll(bm));
+                if (bp) pp = atomicAdd(&cur_sh[0], (unsigned int)__popcll(bp));
+            }
+            pm = __shfl(pm, 0);
+            pp = __shfl(pp, 0);
+            int i = (int)(v & ~DEFER_MARK);
+            if (a.perm && valid) i = a.perm_i0 + a.perm[i - a.perm_i0];
+            if (plain) {
+                const unsigned long long p = base + pp + lanes_below(bp);
+                key_j[p] = (uint32_t)(cj[x] + a.j0);
+                val_i[p] = (uint32_t)i;
+            } else if (marked && d_fits) {
+                const unsigned long long p = base_d + pm + lanes_below(bm);
+                a.d_i[p] = i;
+                a.d_j[p] = cj[x] + a.j0;
+            }
+        }
+        return;
+    }
     if (threadIdx.x == 0) base_sh = atomicAdd(n_out, (unsigned long long)n);
     __syncthreads();
     const unsigned long long base = base_sh;
@@ -230,16 +286,22 @@ struct WavePairs {
     uint32_t j[64];
 };
 
+// With a floor (deferred rescoring, ScreenArgs::floor) the screen has three outcomes: drop (as before: the pair cannot
+// exceed the radius), defer (its exact score is proven to lie in (radius, floor]: it joins the deferred set D, score-less)
+// and exact (everything else: the survivors).
 template <bool FRAG>
 __global__ __launch_bounds__(256) void f16_screen_kernel(ScreenArgs a) {
     if (*a.overflow) return;
-    __shared__ WavePairs wave_pairs[4];
+    __shared__ WavePairs wave_pairs[4], wave_defer[4];
     WavePairs& buf = wave_pairs[threadIdx.x >> 6];
-    int pend = 0;
+    WavePairs& dbuf = wave_defer[threadIdx.x >> 6];
+    int pend = 0, dpend = 0;
     const int lane = threadIdx.x & 63, g = lane & 3;
     const long long n_thr = (4 * a.n + 63) & ~63ll;
     const int npiece = a.dpadh / 8, nks = a.dpadh / 16;
     const float radius = a.row_thr ? 0.0f : *a.radius;
+    const float floor_v = !a.row_thr && a.floor ? *a.floor : INFINITY;
+    const bool defer_on = floor_v < INFINITY;
     const f16x8* __restrict__ Rp = reinterpret_cast<const f16x8*>(a.Rh);
     auto flush = [&]() {
         if (pend == 0) return;
@@ -253,6 +315,24 @@ __global__ __launch_bounds__(256) void f16_screen_kernel(ScreenArgs a) {
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         pend = 0;
+    };
+    auto flush_defer = [&]() {
+        if (dpend == 0) return;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        unsigned long long base = 0;
+        if (lane == 0) {
+            base = atomicAdd(a.d_count, (unsigned long long)dpend);
+            atomicAdd(a.d_total, (unsigned long long)dpend);
+        }
+        base = __shfl(base, 0);
+        if ((long long)(base + dpend) > a.d_cap) {
+            if (lane == 0) atomicOr(a.overflow, 1);
+        } else if (lane < dpend) {
+            a.d_i[base + lane] = (int32_t)dbuf.i[lane];
+            a.d_j[base + lane] = (int32_t)dbuf.j[lane];
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        dpend = 0;
     };
     for (long long x = (long long)blockIdx.x * 256 + threadIdx.x; x < n_thr; x += (long long)gridDim.x * 256) {
         const long long c = x >> 2;
@@ -278,8 +358,23 @@ __global__ __launch_bounds__(256) void f16_screen_kernel(ScreenArgs a) {
         acc += __shfl_xor(acc, 1);
         acc += __shfl_xor(acc, 2);
         const float eps = (a.c1 * a.qn[i] * a.rn[j] + a.c2 * (a.qn[i] + a.rn[j]) + a.c3) * 1.001f;
-        const bool pass = valid && g == 0 &&
-                          (!(eps < INFINITY) || (a.row_thr ? acc >= candidate_edge(a.row_thr[i], eps) : acc > candidate_edge(radius, eps)));
+        bool pass = valid && g == 0 &&
+                    (!(eps < INFINITY) || (a.row_thr ? acc >= candidate_edge(a.row_thr[i], eps) : acc > candidate_edge(radius, eps)));
+        if (defer_on) {
+            // exact >= acc - eps > radius and exact <= acc + eps <= floor, the sums' own roundings taken off as in
+            // candidate_edge (an infinite or NaN bound: no score lies in the band)
+            const float lo = (radius + eps) + 2.4e-7f * (fabsf(radius) + eps);
+            const bool defer = pass && acc > lo && acc <= candidate_edge(floor_v, eps);
+            pass = pass && !defer;
+            const unsigned long long md = __ballot(defer);
+            if (defer) {
+                const int p = dpend + __popcll(md & ((1ull << lane) - 1));
+                dbuf.i[p] = i;
+                dbuf.j[p] = j;
+            }
+            dpend += __popcll(md);
+            if (dpend > 48) flush_defer();
+        }
         const unsigned long long m = __ballot(pass);  // <= 16 per pass
         if (pass) {
             const int p = pend + __popcll(m & ((1ull << lane) - 1));
@@ -290,6 +385,7 @@ __global__ __launch_bounds__(256) void f16_screen_kernel(ScreenArgs a) {
         if (pend > 48) flush();
     }
     flush();
+    flush_defer();
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(a.n_cand_total, (unsigned long long)a.n);
 }
 

@@ -74,7 +74,16 @@ __global__ __launch_bounds__(256) void select_hist_kernel(SelectCtl* c, const fl
     if (lh[threadIdx.x]) atomicAdd(&c->hist[threadIdx.x], lh[threadIdx.x]);
 }
 
-__global__ void select_pick_kernel(SelectCtl* c, int shift) {
+// mode (what the selected score is for, decided at shift 0):
+//   PICK_RADIUS  the ordinary round: radius <- the selected score
+//   PICK_TRIAL   an event with the deferred set D left out (select_begin_defer_kernel).  The selected score v is the
+//                (K+1)-th best of the scored hits A alone; every pair of D lies at or below the floor, so with v >= floor v
+//                is the (K+1)-th best of A and D together, ties included, and every pair of D falls to the strict
+//                re-filter: radius <- v, D <- empty.  With v < floor nothing is decided: the round is called off and
+//                the host re-scores D first (need_force)
+//   PICK_FLOOR   floor <- the selected score; the radius stays
+enum { PICK_RADIUS = 0, PICK_TRIAL = 1, PICK_FLOOR = 2 };
+__global__ void select_pick_kernel(SelectCtl* c, int shift, int mode) {
     if (!c->active) return;
     __shared__ unsigned int h[256];
     h[threadIdx.x] = c->hist[threadIdx.x];
@@ -89,10 +98,63 @@ __global__ void select_pick_kernel(SelectCtl* c, int shift) {
         c->rank = rank;
         c->prefix |= (unsigned int)d << shift;
         c->prefix_mask |= 255u << shift;
-        if (shift == 0) c->radius = key2f(c->prefix);
+        if (shift == 0) {
+            const float v = key2f(c->prefix);
+            if (mode == PICK_FLOOR) {
+                c->floor = v;
+            } else if (mode == PICK_TRIAL && c->n_d > 0 && !(v >= c->floor)) {
+                c->need_force = 1;
+            } else {
+                c->radius = v;
+                if (mode == PICK_TRIAL) {
+                    c->n_rethreshold += 1;
+                    c->ev_ok += c->n_d > 0 ? 1u : 0u;
+                    c->n_d = 0;
+                }
+                c->floor = INFINITY;  // (a floor belongs to the radius it was chosen under)
+            }
+        }
     }
     __syncthreads();
     c->hist[threadIdx.x] = 0;
+    // (a trial that was called off: the compaction behind it must not run)
+    if (shift == 0 && mode == PICK_TRIAL && threadIdx.x == 0 && c->need_force) c->active = 0;
+}
+
+// The event's predicate with D outstanding: kept = scored + deferred hits.  The selection runs over the scored hits alone,
+// which needs K + 1 of them; with fewer the host re-scores D first.
+__global__ void select_begin_defer_kernel(SelectCtl* c, unsigned long long max_results, unsigned long long min_results) {
+    if (threadIdx.x < 256) c->hist[threadIdx.x] = 0;
+    if (threadIdx.x == 0) {
+        const bool pred = !c->overflow && c->n + c->n_d > max_results;
+        const bool can = c->n > min_results;
+        c->active = pred && can ? 1 : 0;
+        c->need_force = pred && !can ? 1 : 0;
+        c->prefix = 0;
+        c->prefix_mask = 0;
+        c->rank = min_results;
+        c->n_tmp = 0;
+    }
+}
+
+// floor <- the score of 0-based descending rank `rank` among the scored hits (none with fewer hits than that)
+__global__ void select_begin_floor_kernel(SelectCtl* c, unsigned long long rank) {
+    if (threadIdx.x < 256) c->hist[threadIdx.x] = 0;
+    if (threadIdx.x == 0) {
+        c->active = !c->overflow && c->n > rank ? 1 : 0;
+        c->floor = INFINITY;
+        c->prefix = 0;
+        c->prefix_mask = 0;
+        c->rank = rank;
+        c->n_tmp = 0;
+    }
+}
+
+// D has been re-scored into the kept hits (or is dropped with a search that overflowed)
+__global__ void defer_reset_kernel(SelectCtl* c) {
+    c->n_d = 0;
+    c->need_force = 0;
+    c->floor = INFINITY;
 }
 
 // copy hits with score > radius from A to B
@@ -176,7 +238,10 @@ __global__ void ctl_init_kernel(SelectCtl* c, float radius) {
     unsigned int* w = reinterpret_cast<unsigned int*>(c);
     for (unsigned x = threadIdx.x; x < sizeof(SelectCtl) / 4; x += blockDim.x) w[x] = 0u;
     __syncthreads();
-    if (threadIdx.x == 0) c->radius = radius;
+    if (threadIdx.x == 0) {
+        c->radius = radius;
+        c->floor = INFINITY;
+    }
 }
 int launch_ctl_init(SelectCtl* ctl, float radius, hipStream_t stream) {
     static_assert(sizeof(SelectCtl) % 4 == 0, "SelectCtl is cleared word by word");
@@ -191,11 +256,46 @@ int enqueue_rethreshold(SelectCtl* ctl, HitView a, HitView b, unsigned long long
     hipLaunchKernelGGL(select_begin_kernel, dim3(1), dim3(256), 0, stream, ctl, 2 * K, K);
     for (int shift = 24; shift >= 0; shift -= 8) {
         hipLaunchKernelGGL(select_hist_kernel, dim3(GRID), dim3(256), 0, stream, ctl, a.s, shift);
-        hipLaunchKernelGGL(select_pick_kernel, dim3(1), dim3(256), 0, stream, ctl, shift);
+        hipLaunchKernelGGL(select_pick_kernel, dim3(1), dim3(256), 0, stream, ctl, shift, (int)PICK_RADIUS);
     }
     hipLaunchKernelGGL(select_compact_kernel, dim3(GRID), dim3(256), 0, stream, ctl, a.i, a.j, a.s, b.i, b.j, b.s);
     hipLaunchKernelGGL(select_copyback_kernel, dim3(GRID), dim3(256), 0, stream, ctl, b.i, b.j, b.s, a.i, a.j, a.s);
     hipLaunchKernelGGL(select_end_kernel, dim3(1), dim3(1), 0, stream, ctl);
+    VSC_HIP(hipGetLastError());
+    return VSC_OK;
+}
+
+// The same round with the deferred set D outstanding: "if n + n_d > 2K: radius <- (K+1)-th best of the scored hits, if
+// that is provably the (K+1)-th best of all kept hits" (select_pick_kernel, PICK_TRIAL); else ctl->need_force is set and
+// nothing has changed.  The caller reads the control block afterwards.
+int enqueue_rethreshold_deferred(SelectCtl* ctl, HitView a, HitView b, unsigned long long K, hipStream_t stream) {
+    constexpr int GRID = 1024;
+    hipLaunchKernelGGL(select_begin_defer_kernel, dim3(1), dim3(256), 0, stream, ctl, 2 * K, K);
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        hipLaunchKernelGGL(select_hist_kernel, dim3(GRID), dim3(256), 0, stream, ctl, a.s, shift);
+        hipLaunchKernelGGL(select_pick_kernel, dim3(1), dim3(256), 0, stream, ctl, shift, (int)PICK_TRIAL);
+    }
+    hipLaunchKernelGGL(select_compact_kernel, dim3(GRID), dim3(256), 0, stream, ctl, a.i, a.j, a.s, b.i, b.j, b.s);
+    hipLaunchKernelGGL(select_copyback_kernel, dim3(GRID), dim3(256), 0, stream, ctl, b.i, b.j, b.s, a.i, a.j, a.s);
+    hipLaunchKernelGGL(select_end_kernel, dim3(1), dim3(1), 0, stream, ctl);
+    VSC_HIP(hipGetLastError());
+    return VSC_OK;
+}
+
+// ctl->floor <- the (rank + 1)-th best score of the kept hits `s` (+inf with fewer): the second rank of the radix select
+int enqueue_floor_select(SelectCtl* ctl, const float* s, unsigned long long rank, hipStream_t stream) {
+    constexpr int GRID = 1024;
+    hipLaunchKernelGGL(select_begin_floor_kernel, dim3(1), dim3(256), 0, stream, ctl, rank);
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        hipLaunchKernelGGL(select_hist_kernel, dim3(GRID), dim3(256), 0, stream, ctl, s, shift);
+        hipLaunchKernelGGL(select_pick_kernel, dim3(1), dim3(256), 0, stream, ctl, shift, (int)PICK_FLOOR);
+    }
+    VSC_HIP(hipGetLastError());
+    return VSC_OK;
+}
+
+int launch_defer_reset(SelectCtl* ctl, hipStream_t stream) {
+    hipLaunchKernelGGL(defer_reset_kernel, dim3(1), dim3(1), 0, stream, ctl);
     VSC_HIP(hipGetLastError());
     return VSC_OK;
 }

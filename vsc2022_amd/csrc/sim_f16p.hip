@@ -72,6 +72,18 @@ __device__ __forceinline__ void tile_mma(const char* smem, const int (&abase)[8]
     }
 }
 
+// Deferred rescoring (SimF16PArgs::floor): the band of fp16 scores whose exact score is proven to lie in (radius, floor],
+// for the lane's column, derived on the flagged-block path from what is live there -- the column's candidate edge `thr`
+// and the two wave-uniform scalars -- so that no per-lane value is added to the tile loop.  e = radius - thr is at least
+// the column's error bound eps (candidate_edge only ever lowers the edge); then acc > lo >= radius + e proves
+// exact > radius and acc <= hi <= floor - e proves exact <= floor, with the roundings of both sums taken off as in
+// candidate_edge.  floor = +inf (off), an infinite or NaN bound: hi is NaN and no score lies in the band.
+__device__ __forceinline__ void defer_band(float radius, float floor_v, float thr, float& lo, float& hi) {
+    const float e = (radius - thr) * 1.000001f;
+    lo = (radius + e) + 2.4e-7f * (fabsf(radius) + e);
+    hi = candidate_edge(floor_v, e);
+}
+
 // Candidates of one wave tile -> the wave's PRIVATE segment of the candidate list (no atomics, no scans; a
 // shared atomic tail only when the segment is full).  Per 32x32 block one question first (its per-lane
 // maximum is known), then one ballot per accumulator register of the few blocks that hold a candidate.
@@ -83,7 +95,8 @@ template <bool ROWTHR>
 __device__ __forceinline__ void emit_candidates(const SimF16PArgs& a, const bool (&all)[2], const float (&thr)[2],
                                                 const float (&eps)[2], const float* rt, const float (&rtmin)[4],
                                                 int row0, int col0, bool interior, const f32x16 (&acc)[4][2],
-                                                const float (&bm)[4][2], int64_t seg_base, int& count, TailExt* ext) {
+                                                const float (&bm)[4][2], int64_t seg_base, int& count, TailExt* ext,
+                                                float radius, float floor_v) {
     // C layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
 #pragma unroll
     for (int m = 0; m < 4; ++m)
@@ -94,6 +107,8 @@ __device__ __forceinline__ void emit_candidates(const SimF16PArgs& a, const bool
             // k-NN: the row thresholds of the lane's 16 rows of this block are looked up by row index: the lane id
             // is taken once per flagged block (live inside the block only)
             const int ln_blk = ROWTHR ? lane_now() : 0;
+            float dlo = INFINITY, dhi = -INFINITY;
+            if (!ROWTHR) defer_band(radius, floor_v, thr[n], dlo, dhi);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int rb = m * 32 + (r & 3) + 8 * (r >> 2);  // + 4 * (lane >> 5) = row inside the panel
@@ -117,7 +132,8 @@ __device__ __forceinline__ void emit_candidates(const SimF16PArgs& a, const bool
                 if (!cand_reserve(a.list, seg_base, count, total, ln, ext, pos)) continue;
                 if (mine) {
                     pos += lanes_below(ok);
-                    a.list.i[pos] = a.i0 + i;
+                    const bool defer = !ROWTHR && acc[m][n][r] > dlo && acc[m][n][r] <= dhi;
+                    a.list.i[pos] = (a.i0 + i) | (defer ? (int)DEFER_MARK : 0);
                     a.list.j[pos] = j;
                 }
             }
@@ -134,7 +150,8 @@ __device__ __forceinline__ void emit_candidates(const SimF16PArgs& a, const bool
 // (per-lane bit masks + a wave prefix sum) gave 310 ms there and 354 against 348 ms on the k-NN (k = 1), and is gone.
 __device__ __forceinline__ void emit_candidates_seg(const SimF16PArgs& a, const float (&thr)[2], int row0, int col0,
                                                     const f32x16 (&acc)[4][2], const float (&bm)[4][2],
-                                                    __amdgpu_buffer_rsrc_t rs_i, __amdgpu_buffer_rsrc_t rs_j, int& count) {
+                                                    __amdgpu_buffer_rsrc_t rs_i, __amdgpu_buffer_rsrc_t rs_j, int& count,
+                                                    float radius, float floor_v) {
 #pragma unroll
     for (int m = 0; m < 4; ++m)
 #pragma unroll
@@ -143,6 +160,8 @@ __device__ __forceinline__ void emit_candidates_seg(const SimF16PArgs& a, const 
             const int ln = lane_now();  // (live inside the block only, see above)
             const int ibase = a.i0 + row0 + m * 32 + 4 * (ln >> 5);
             const int j = col0 + n * 32 + (ln & 31);
+            float dlo, dhi;
+            defer_band(radius, floor_v, thr[n], dlo, dhi);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const bool cand = acc[m][n][r] > thr[n];
@@ -150,7 +169,8 @@ __device__ __forceinline__ void emit_candidates_seg(const SimF16PArgs& a, const 
                 if (hits == 0ull) continue;
                 if (cand) {
                     const int off = (count + (int)lanes_below(hits)) << 2;
-                    __builtin_amdgcn_raw_buffer_store_b32(ibase + (r & 3) + 8 * (r >> 2), rs_i, off, 0, 0);
+                    const bool defer = acc[m][n][r] > dlo && acc[m][n][r] <= dhi;
+                    __builtin_amdgcn_raw_buffer_store_b32((ibase + (r & 3) + 8 * (r >> 2)) | (defer ? (int)DEFER_MARK : 0), rs_i, off, 0, 0);
                     __builtin_amdgcn_raw_buffer_store_b32(j, rs_j, off, 0, 0);
                 }
                 count += __popcll(hits);
@@ -182,6 +202,7 @@ __global__ __launch_bounds__(512) void sim_f16p_kernel(SimF16PArgs a) {
         for (int u = 0; u < 8; ++u) abase[u] = rl * 256 + ((((2 * u) | hi) ^ r15) << 4);
     }
     const float radius = ROWTHR ? 0.0f : *a.radius;
+    const float floor_v = !ROWTHR && a.floor ? *a.floor : INFINITY;  // (+inf: nothing is deferred)
     const int seg = blockIdx.x * 8 + wave;  // this wave's private segment of the candidate list
     const int64_t seg_base = (int64_t)seg * a.list.seg_cap;
     int count = 0;
@@ -324,10 +345,10 @@ __global__ __launch_bounds__(512) void sim_f16p_kernel(SimF16PArgs a) {
             if (__any(any_blk)) {
                 const bool interior = panel * PR + PR <= a.nq && col0 + 64 <= a.nr;
                 if (!ROWTHR && interior && !all[0] && !all[1] && count + 8192 <= a.list.seg_cap)
-                    emit_candidates_seg(a, thr, panel * PR, col0, acc, bm, rs_ci, rs_cj, count);
+                    emit_candidates_seg(a, thr, panel * PR, col0, acc, bm, rs_ci, rs_cj, count, radius, floor_v);
                 else
                     emit_candidates<ROWTHR>(a, all, thr, eps, rt_sh, rtmin, panel * PR, col0, interior, acc, bm,
-                                            seg_base, count, &tail_sh[wave]);
+                                            seg_base, count, &tail_sh[wave], radius, floor_v);
             }
         }
     }

@@ -371,6 +371,10 @@ class FlatIndex:
         cand, hits = ctypes.c_int64(0), ctypes.c_int64(0)
         _lib.check(_lib.lib().vsc_index_search_stats(self._h, ctypes.byref(cand), ctypes.byref(hits)))
         out["candidates"] = cand.value
+        # deferred rescoring of the last global_topk (option "defer"): pairs deferred, pairs of them re-scored after all,
+        # events decided with the deferred set left out, events that needed it re-scored first
+        for name in ("deferred", "defer_forced", "defer_events_ok", "defer_events_forced"):
+            out[name] = int(self.get_option(name))
         return out
 
 
