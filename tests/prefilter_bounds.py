@@ -28,6 +28,7 @@ import numpy as np
 FRAC = 63.0 / 128.0      # int8: residual of every non-extreme coordinate, in steps of the scale
 M = 100.0                # int8: integer part of those coordinates
 F16_MID = 1.0 + 2.0 ** -11 - 2.0 ** -22     # fp16: just below the midpoint between 1 and 1 + 2^-10
+F16_MID_UP = 1.0 + 2.0 ** -11 + 2.0 ** -22  # fp16: just above it (defer_radius_case: every coordinate rounds up)
 
 # fraction of c1 |q||r| that the fp16 construction reaches, asserted per dimension (D = 1000 pads to 1024)
 F16_REACH = {64: 0.95, 512: 0.85, 768: 0.75, 1000: 0.75}
@@ -59,16 +60,17 @@ def row_exponent(kind, d):
     return -int(round(math.log2(base * math.sqrt(d))))
 
 
-def magnitudes(kind, d, level=0):
+def magnitudes(kind, d, level=0, mid=F16_MID):
     """|coordinates| of a row.  level 0: queries, partners, noise; -1: decoy (last coordinate one int8 step / 2^-11
-    smaller: the score drops below the partner's in the chain's last addition); +1 (k-NN): one step larger"""
+    smaller: the score drops below the partner's in the chain's last addition); +1 (k-NN): one step larger.
+    mid (fp16): F16_MID, all coordinates round down (low < exact), or F16_MID_UP, all round up (low > exact)"""
     k = row_exponent(kind, d)
     if kind == "i8":
         a = np.full(d, (M + FRAC) * 2.0 ** k)
         a[0] = 127.0 * 2.0 ** k
         a[d - 1] += level * 2.0 ** k
     else:
-        a = np.full(d, F16_MID * 2.0 ** k)
+        a = np.full(d, mid * 2.0 ** k)
         a[d - 1] += level * 2.0 ** (k - 11)
     return a
 
@@ -258,13 +260,16 @@ class PairBound:
             self.low = (hx * hy).sum(1)
             nx, ny = np.linalg.norm(x, axis=1), np.linalg.norm(y, axis=1)
             self.eps = f16_eps(np.linalg.norm(case.q.astype(np.float64), axis=1).max() * 1.0005, ny * 1.0005, d)
+            # (the fp16 screen of rescore.hip builds its bound from the pair's own query row, not the panel's largest)
+            self.eps_pair = f16_eps(nx * 1.0005, ny * 1.0005, d)
             self.c1qr = f16_coefficients(d)[0] * nx * ny
             self.unit = None
         self.shift = self.b + self.c
         self.err = self.exact - self.shift - self.low
 
     def reach(self):
-        """err / eps, and for fp16 err / (c1 |q||r|): the share of the bound that the rounding errors really use"""
+        """err / eps, and for fp16 err / (c1 |q||r|): the share of the bound that the rounding errors really use
+        (negative where the low-precision score lies above the exact one: the F16_MID_UP rows)"""
         return self.err / self.eps, (None if self.c1qr is None else self.err / self.c1qr)
 
     def slack(self, t):
@@ -282,3 +287,160 @@ class PairBound:
         """(t - shift - slack - low) / eps against the exact threshold t of the whole score: the kernel keeps the pair
         iff this is below 1 (up to its slack), and a bound f eps would lose it iff it is above f"""
         return (np.asarray(t, np.float64) - self.shift - self.slack(t) - self.low) / self.eps
+
+
+# ---------------------------------------------------------------- deferred rescoring: the band (radius, floor]
+# A pre-filtered batch of the global top-K leaves the exact score of a candidate uncomputed when its fp16 score proves
+# that score to lie in (radius, floor] (api_search.hip "the deferred set"): low > radius + e and low <= floor - e.  The
+# two cases below bring planted pairs within (f, 1) e of one of those edges, on the side where a too small e is wrong:
+#   defer_floor_case   rows that round down (low < exact): exact = s > floor = s_d, low ~0.9 eps below s.  A narrower
+#                      e puts them into D; the next event is still decided without D and drops them from the result.
+#   defer_radius_case  rows that round up (low > exact): exact = s <= radius = s_u, low ~0.9 eps above s.  A narrower
+#                      e puts them into D; D is re-scored at the end and the search reports pairs at or below the radius.
+# "Plain" references sign(q_i) c 2^k (exact in fp16) score ~c s, hundreds of eps away from every edge: those with
+# radius < c s <= floor are the pairs a correct band defers, the others set radius and floor.
+DEFER_NQ, DEFER_K, DEFER_NR = 224, 300, 2048 + 37    # schedule 32 + 64 + 128 rows; the last column tile holds 37
+
+
+class DeferCase(Case):
+    """roles[name] = (query rows, references) of the pairs of one role; K, side ('floor' / 'radius')"""
+
+    def __init__(self, q, r, partner, d, side, roles):
+        super().__init__(q, r, partner, "f16", d)
+        self.side, self.roles, self.K = side, roles, DEFER_K
+
+    def pairs(self, *names):
+        rows = np.concatenate([self.roles[n][0] for n in names])
+        refs = np.concatenate([self.roles[n][1] for n in names])
+        return rows, refs
+
+
+def _defer_assemble(d, side, mid, entries_of, nr, seed):
+    """entries_of(i) = [(role, level or None, plain factor or None), ...] of query row i.  The references of every
+    fourth later row go behind the noise, their planted partners last: the last, partial 64-column tile holds planted
+    pairs of the 64-row batch (a partial panel) and of the 128-row batch; the other partners lie in interior tiles."""
+    rng = np.random.default_rng(seed)
+    nq, k = DEFER_NQ, row_exponent("f16", d)
+    sq = _signs(rng, nq, d)
+    q = sq * magnitudes("f16", d, 0, mid)
+    front, tail_other, tail_planted = [], [], []
+    for i in range(nq):
+        for role, level, c in entries_of(i):
+            vec = sq[i] * (magnitudes("f16", d, level, mid) if c is None else np.full(d, c * 2.0 ** k))
+            late = i >= 32 and i % 4 == 3
+            (tail_planted if late and role == "planted" else tail_other if late else front).append((role, i, vec))
+    n_noise = nr - len(front) - len(tail_other) - len(tail_planted)
+    assert n_noise >= 512 and len(tail_planted) >= nr % 64 > 0, (n_noise, len(tail_planted), nr)
+    noise = _signs(rng, n_noise, d) * magnitudes("f16", d, 0, mid)
+    tail = tail_other + tail_planted
+    r = np.concatenate([np.array([v for _, _, v in front]), noise, np.array([v for _, _, v in tail])])
+    where = [(role, i, n) for n, (role, i, _) in enumerate(front)]
+    where += [(role, i, len(front) + n_noise + n) for n, (role, i, _) in enumerate(tail)]
+    roles = {}
+    for role in sorted({w[0] for w in where}):
+        roles[role] = (np.array([i for ro, i, _ in where if ro == role]), np.array([j for ro, _, j in where if ro == role]))
+    partner = np.full(nq, -1, np.int64)
+    partner[roles["planted"][0]] = roles["planted"][1]
+    q32, r32 = q.astype(np.float32), r.astype(np.float32)
+    assert np.array_equal(q32.astype(np.float64), q) and np.array_equal(r32.astype(np.float64), r)  # all exact
+    return DeferCase(q32, r32, partner, d, side, roles)
+
+
+def defer_floor_case(d, nr=DEFER_NR, seed=2):
+    """Rows 0..31: 9 decoys (s_d) and one plain 0.75 row each: the event at row 32 sets the radius to the 0.75 score, the
+    288 decoys stay, every rank gives floor = s_d.  Rows 32..223: the partner (s > s_d, not provably <= floor), one more
+    decoy (s_d = floor: not provably either), a plain 0.875 row (deferred) and on every third row a plain 1.25 row."""
+    def entries(i):
+        if i < 32:
+            return [("decoy", -1, None)] * 9 + [("plain075", None, 0.75)]
+        return ([("planted", 0, None), ("decoy2", -1, None), ("plain0875", None, 0.875)]
+                + ([("plain125", None, 1.25)] if i % 3 == 0 else []))
+    return _defer_assemble(d, "floor", F16_MID, entries, nr, seed)
+
+
+def defer_radius_case(d, nr=DEFER_NR, seed=3):
+    """Rows 0..31: 4 plain 1.25 rows and 6 decoys one step larger (s_u) each: the event at row 32 sets the radius to s_u,
+    the 128 plain rows stay and their score is the floor.  Rows 32..223: the partner (s < s_u = radius, its fp16 score
+    ~0.9 eps above s: not provably > radius) and on every second row a plain 1.125 row (deferred)."""
+    def entries(i):
+        if i < 32:
+            return [("plain125", None, 1.25)] * 4 + [("decoy_up", 1, None)] * 6
+        return [("planted", 0, None)] + ([("plain1125", None, 1.125)] if i % 2 == 0 else [])
+    return _defer_assemble(d, "radius", F16_MID_UP, entries, nr, seed)
+
+
+def defer_deferrable(c):
+    """the role a correct band defers, all of it and nothing else"""
+    return "plain0875" if c.side == "floor" else "plain1125"
+
+
+def score_matrix(c):
+    """fp32 scores of all pairs: the chain score of every role's pairs; every other pair (random signs against random
+    signs, far below every threshold of the schedule) by a float64 product rounded once.  Returns S and the mask of the
+    role pairs."""
+    S = (c.q.astype(np.float64) @ c.r.astype(np.float64).T).astype(np.float32)
+    role = np.zeros(S.shape, bool)
+    for rows, refs in c.roles.values():
+        S[rows, refs] = chain(c.q[rows], c.r[refs])
+        role[rows, refs] = True
+    return S, role
+
+
+def replay_schedule(S, K):
+    """the reference's schedule on a score matrix (range_search_max_results: batches of 32, 64, ... rows, an event when
+    more than 2K hits are kept): [(rows seen, kept before the event's test, event?, radius behind the boundary)]"""
+    radius, kept, out, bs, i0 = np.float32(-1e10), np.empty(0, np.float32), [], 32, 0
+    while i0 < len(S):
+        i1 = min(len(S), i0 + bs)
+        new = S[i0:i1].ravel()
+        kept = np.concatenate([kept, new[new > radius]])
+        n, event = len(kept), len(kept) > 2 * K
+        if event:
+            radius = np.sort(kept)[::-1][K]
+            kept = kept[kept > radius]
+        out.append((i1, n, event, radius))
+        if bs < 20000:
+            bs *= 2
+        i0 = i1
+    return out
+
+
+def _edge(t, e):
+    """prefilter_dev.h candidate_edge"""
+    return (t - e) - 2.4e-7 * (np.abs(t) + e)
+
+
+def defer_band(b, radius, floor, route, f_lo=1.0, f_hi=1.0):
+    """The band of fp16 scores that the kernels defer, for the pairs of PairBound b: (candidate edge, lo, hi).
+      route 'panel'   sim_f16p.hip defer_band: e = (radius - thr) 1.000001, thr = the column's candidate edge (bound of
+                      the panel's largest query norm)
+      route 'screen'  rescore.hip f16_screen_kernel: e = the pair's own eps
+      lo = (radius + e) + 2.4e-7 (|radius| + e), hi = (floor - e) - 2.4e-7 (|floor| + e)
+    f_lo, f_hi scale e on one edge: what a wrong band would be (1: the kernels'; 0: no bound; -1: the wrong sign)."""
+    radius, floor = np.float64(radius), np.float64(floor)
+    if route == "panel":
+        thr = _edge(radius, b.eps)
+        e = (radius - thr) * 1.000001
+    else:
+        assert route == "screen", route
+        thr = _edge(radius, b.eps_pair)
+        e = b.eps_pair
+    e_lo, e_hi = f_lo * e, f_hi * e
+    return thr, (radius + e_lo) + 2.4e-7 * (abs(radius) + e_lo), _edge(floor, e_hi)
+
+
+def defer_margins(c, rows, refs, radius, floor, route):
+    """(low - lo) / eps and (hi - low) / eps of the pairs: how far inside the band's two edges the fp16 score lies, in
+    units of the bound.  A pair is deferred iff the first is > 0 and the second >= 0; a pair with exact score outside
+    (radius, floor] must have one of them below 0, and is `-m` eps away from being deferred wrongly."""
+    b = PairBound(c, rows, refs)
+    _, lo, hi = defer_band(b, radius, floor, route)
+    eps = b.eps if route == "panel" else b.eps_pair
+    return (b.low - lo) / eps, (hi - b.low) / eps
+
+
+def defer_predicted(c, rows, refs, radius, floor, route, f_lo=1.0, f_hi=1.0):
+    """which of the pairs the (possibly wrong, see defer_band) band defers: candidates whose fp16 score lies in it"""
+    b = PairBound(c, rows, refs)
+    thr, lo, hi = defer_band(b, radius, floor, route, f_lo, f_hi)
+    return (b.low > thr) & (b.low > lo) & (b.low <= hi)

@@ -50,6 +50,10 @@ def data(name):
     elif name == "l2":
         rng = np.random.default_rng(11)
         q, r = unit(rng, 150, 24), unit(rng, 170, 24)
+    elif name == "overflow":  # the data of test_overflow_retry_in_fresh_process (unnormalised; references drawn first)
+        rng = np.random.default_rng(5)
+        r = rng.standard_normal((900, 64)).astype(np.float32)
+        q = rng.standard_normal((300, 64)).astype(np.float32)
     else:
         raise KeyError(name)
     q.setflags(write=False)
@@ -58,11 +62,13 @@ def data(name):
 
 
 @functools.lru_cache(maxsize=None)
-def reference(name, K, metric=0):
+def reference(name, K, metric=0, codec="Flat"):
+    """(an SQfp16 index is the Flat index of the rows it decodes to: tests/test_gpu_codec.py)"""
     import oracle as orc
+    from codec_rows import dec
 
     q, r = data(name)
-    return orc.global_threshold_search(q, r, K, metric, return_info=True)
+    return orc.global_threshold_search(q, r if codec == "Flat" else dec(r), K, metric, return_info=True)
 
 
 def boundaries(name, K):
@@ -87,14 +93,14 @@ def boundaries(name, K):
     return out
 
 
-def search(name, K, route, defer, margin=None, metric=0):
+def search(name, K, route, defer, margin=None, metric=0, codec="Flat"):
     from vsc2022_amd.vsc.index import FlatIndex
 
     q, r = data(name)
     opts = dict(ROUTES[route], defer=defer)
     if margin is not None:
         opts["defer_margin"] = margin
-    idx = FlatIndex(q.shape[1], metric, options=opts)
+    idx = FlatIndex(q.shape[1], metric, options=opts, codec=codec)
     idx.add(r)
     i, j, s, radius = idx.global_topk(q, K)
     st = {k: int(idx.get_option(k)) for k in STATS}
@@ -107,11 +113,11 @@ def same(a, b):
             and bits(a[3]) == bits(b[3]))
 
 
-def check(name, K, route, defer, margin=None, metric=0):
+def check(name, K, route, defer, margin=None, metric=0, codec="Flat"):
     """The search with `defer` equals defer = 0 and the oracle; returns its statistics."""
-    got, st = search(name, K, route, defer, margin, metric)
-    off, st0 = search(name, K, route, 0, None, metric)
-    oi, oj, os_, info = reference(name, K, metric)
+    got, st = search(name, K, route, defer, margin, metric, codec)
+    off, st0 = search(name, K, route, 0, None, metric, codec)
+    oi, oj, os_, info = reference(name, K, metric, codec)
     want = (oi, oj, os_, np.float32(info["radius"]))
     assert same(off, want), (name, K, route, "defer = 0 differs from the oracle")
     assert same(got, want), (name, K, route, defer, margin, st)
@@ -192,3 +198,74 @@ def test_l2_metric(gpu, orc, K):
 @pytest.mark.parametrize("name,K", CASES + [("carry", 4000), ("ties", 777)])
 def test_default_mode_small_search(gpu, orc, name, K):
     check(name, K, "default", 1)
+
+
+@pytest.mark.parametrize("defer", [1, 2])
+@pytest.mark.parametrize("route", ["fp16", "int8"])
+@pytest.mark.parametrize("name,K", CASES)
+def test_sqfp16_index_defers(gpu, orc, name, K, route, defer):
+    """An index that keeps its references as half floats: the panel kernel and the screen read the store itself, the
+    exact stage decodes it.  Equal to defer = 0 on the same index and to the oracle over the decoded rows."""
+    st = check(name, K, route, defer, codec="SQfp16")
+    assert st["deferred"] > 0, st
+
+
+@pytest.mark.parametrize("margin", [None, 3.0])
+@pytest.mark.parametrize("route", ["fp16", "int8"])
+def test_kept_hits_overflow_while_d_is_open(gpu, orc, route, margin):
+    """The first batch (32 x 900 = 2K pairs) triggers no event and a floor is chosen behind it; the 64-row batch brings
+    the kept hits to 96 x 900, more than the default buffer holds.  The deferred set takes its share of them: at the
+    default margin the floor lies high and the scored hits still fit, at margin 3 the floor is the score of rank
+    4 (K + 1) / 3 and the scored hits alone outgrow the buffer while the floor is set.  The boundary then finds the
+    overflow flag, D is abandoned and the whole schedule is rerun with a larger buffer (deferred_event, api_search.hip).
+    The statistics are zeroed per attempt: they are those of the rerun, equal to a search that never overflowed.
+    (In that batch the radius is still -1e10.  The screen's band is (radius + eps, floor - eps] and D holds a third of
+    the batch when it overflows; the panel kernel's e = radius - thr includes the 2.4e-7 |radius| = 2400 that the
+    candidate edge takes off for the radius' own rounding, so its band is empty there: the floor is set, D holds
+    nothing yet, and its batches defer after the first event only.)"""
+    from vsc2022_amd.vsc.index import FlatIndex
+
+    name, K = "overflow", 14400
+    q, r = data(name)
+    cap = max(32 * len(r), 2 * K) + 2 * K + 1024      # the default kept-hit buffer (global_topk_impl)
+    b = boundaries(name, K)
+    assert b[0] == (32, 2 * K, False) and b[1] == (96, 96 * len(r), True) and b[1][1] > cap, (b, cap)
+    S = orc.scores(q, r)
+    if margin is not None:
+        # (choose_floor: rank ceil((K + 1) b / b_next (1 + margin)) of the first batch's hits, b = 32, b_next = 96.)  A
+        # pair above the floor cannot be deferred: that many scored hits at least
+        m = int(np.ceil((K + 1.0) * (32.0 / 96.0) * (1.0 + margin)))
+        floor = np.sort(S[:32].ravel())[::-1][m - 1]
+        assert m <= 2 * K and 32 * len(r) + int((S[32:96] > floor).sum()) > cap
+
+    def run(defer):
+        """two searches of one fresh handle: (result, statistics, kernel launches) of each.  The second starts with
+        the buffer the first one ended with."""
+        opts = dict(ROUTES[route], defer=defer)
+        if defer and margin is not None:
+            opts["defer_margin"] = margin
+        idx = FlatIndex(q.shape[1], 0, options=opts)
+        idx.profile(True)
+        idx.add(r)
+        out = []
+        for _ in range(2):
+            i, j, s, radius = idx.global_topk(q, K)
+            p = idx.profile_read(reset=True)
+            st = {k: p[k] for k in STATS}
+            st["n_rethreshold"] = int(idx.get_option("n_rethreshold"))
+            out.append(((i, j, s, np.float32(radius)), st, sum(v for k, v in p.items() if k.endswith("_launches"))))
+        return out
+
+    oi, oj, os_, info = reference(name, K)
+    want = (oi, oj, os_, np.float32(info["radius"]))
+    (off1, st_off1, n_off1), (off2, st_off2, n_off2) = run(0)
+    assert same(off1, want) and same(off2, want)
+    assert n_off1 > n_off2, (n_off1, n_off2)          # the first search ran its schedule twice
+    assert all(st_off1[k] == 0 for k in STATS) and st_off1 == st_off2, (st_off1, st_off2)
+    (got1, st1, n1), (got2, st2, n2) = run(2)
+    assert same(got1, want) and same(got2, want), (st1, st2)
+    assert st1 == st2 and st1["n_rethreshold"] == info["n_rethreshold"], (st1, st2, info)
+    if margin is None or route == "int8":
+        assert st1["deferred"] > 0, st1
+    if margin is not None:
+        assert n1 > n2, (n1, n2)                      # overflowed with D open, and was rerun
