@@ -257,6 +257,44 @@ int vsc_pair_max(const int32_t* hit_i, const int32_t* hit_j, const float* hit_s,
                  int64_t nr_rows, int maps_mem, int32_t* out_q, int32_t* out_r, float* out_s,
                  int64_t* out_first, int64_t cap, int out_mem, int64_t* n_pairs, int device);
 
+/* The same regroup with a choice of aggregation, for hit lists in either order -- the ScoreAggregation extension point of
+ * vsc/candidates.py:14-26 for the four aggregations that run on the device.  One definition for all of them, chosen so
+ * that a host function and a kernel compute the same bits: for one (query video, ref video) pair with hit scores
+ * s_1..s_c (fp32, FINITE: a precondition, not checked) let d be those scores as float64, sorted descending; then
+ *   VSC_AGG_MAX      the largest score (fp32; a run holding both zeros yields +0.0);
+ *   VSC_AGG_SUM      acc = 0.0; for v in d: acc = acc + v -- one IEEE float64 add per hit, in that order -- as float32(acc);
+ *   VSC_AGG_MEAN     the same acc, float32(acc / float64(c));
+ *   VSC_AGG_TOPMEAN  the same loop over the first min(top_m, c) entries of d, divided by float64(min(top_m, c)).
+ * (numpy: np.cumsum(np.sort(x.astype(np.float64))[::-1])[k - 1].)  Equal scores are identical numbers and acc starts at
+ * +0.0, so neither the order of ties nor the sign of a zero can change a result.
+ * hits_order: 1 = the list is in search order (score descending, as vsc_index_global_topk returns it), 0 = any order,
+ * e.g. the (row, rank) order of a k-NN result: the descending order of every pair's scores is then established here.
+ * Output pairs in their FINAL order: first-appearance order over the hit list (the reference's dict order), stably
+ * sorted by the aggregated fp32 score descending with -0.0 == +0.0 (vsc/candidates.py:38-40).  out_q / out_r video
+ * ordinals, out_s the aggregated score, out_first (optional) the index of the pair's first hit in the caller's list,
+ * out_count (optional) its number of hits.  cap >= n suffices; VSC_ERR_CAPACITY with *n_pairs set otherwise.  n < 2^31.
+ * VSC_ERR_INVALID before any launch (and before the device is looked at) for an unknown agg or top_m < 1 with
+ * VSC_AGG_TOPMEAN.  A hit row outside [0, nq_rows) x [0, nr_rows): VSC_ERR_INVALID -- checked on the host for a list in
+ * host memory, by a device-side error word otherwise (the kernel skips the hit: nothing is read outside the maps).
+ * Handle-less family (vsc_set_aux_stream); host or device arrays with the conventions of vsc_pair_max. */
+#define VSC_AGG_MAX 0
+#define VSC_AGG_SUM 1
+#define VSC_AGG_MEAN 2
+#define VSC_AGG_TOPMEAN 3
+int vsc_pair_aggregate(const int32_t* hit_i, const int32_t* hit_j, const float* hit_s, int64_t n, int hits_mem,
+                       const int32_t* row2q, int64_t nq_rows, const int32_t* row2r, int64_t nr_rows, int maps_mem,
+                       int hits_order, int agg, int64_t top_m, int32_t* out_q, int32_t* out_r, float* out_s,
+                       int64_t* out_first, int32_t* out_count, int64_t cap, int out_mem, int64_t* n_pairs, int device);
+
+/* vsc_index_candidates with a choice of aggregation (agg, top_m: as above) and of retrieval: K >= 0 is the global-
+ * threshold search of K hits (vsc/index.py:142-165, hits in search order), K < 0 the vanilla k-NN retrieval with k = -K
+ * (vsc/index.py:108-117,167-177, hits in (row, rank) order).  The hits never leave HBM.  VSC_ERR_INVALID before any
+ * launch for an unknown agg, top_m < 1 with VSC_AGG_TOPMEAN and k > ntotal (an empty k-NN slot has no video).  Outputs as
+ * vsc_index_candidates, pairs in the final order of vsc_pair_aggregate; cap >= min(|K| hits, nq * ntotal) suffices. */
+int vsc_index_candidates_agg(vsc_index_t* idx, const float* q, int64_t nq, int q_mem, int64_t K, const int32_t* row2q,
+                             const int32_t* row2r, int agg, int64_t top_m, int32_t* out_q, int32_t* out_r, float* out_s,
+                             int64_t cap, int64_t* n_pairs, int64_t* n_hits);
+
 /* The final ordering of a hit list on its own: (score desc, query row asc, reference row asc), the order in which
  * VideoIndex._global_threshold_knn_search flattens and stably sorts its hits (vsc/index.py:158-165) -- for callers that
  * assemble a hit list themselves (the sharded schedule, vsc2022_amd/engine.py: the kept hits of the column slices arrive at
@@ -304,7 +342,7 @@ int vsc_argsort_scores(const float* scores, int64_t n, int mem, int32_t* perm, i
 int vsc_merge_topk(const float* scores, const int64_t* ids, int64_t nq, int m, int k, float* out_s, int64_t* out_ids,
                    int device);
 
-/* The stream of the entry points that own no handle on `device` (vsc_pair_max, vsc_sort_hits, vsc_score_histogram, vsc_score_pick,
+/* The stream of the entry points that own no handle on `device` (vsc_pair_max, vsc_pair_aggregate, vsc_sort_hits, vsc_score_histogram, vsc_score_pick,
  * vsc_filter_hits, vsc_argsort_scores, vsc_merge_topk, vsc_row_normalize, vsc_tn_forward_sim, vsc_align_forward_sim):
  * as vsc_index_set_stream. */
 int vsc_set_aux_stream(int device, void* hip_stream, int own);

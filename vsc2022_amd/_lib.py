@@ -38,6 +38,11 @@ TN_MAX_BOXES = 16
 ALIGN_DTW = 1
 ALIGN_DP = 2
 METRIC_MAX_PAIR_ROWS = 8192  # VSC_METRIC_MAX_PAIR_ROWS: predictions + ground-truth rows of one (query, ref) pair
+# aggregations of vsc_pair_aggregate / vsc_index_candidates_agg (VSC_AGG_*)
+AGG_MAX = 0
+AGG_SUM = 1
+AGG_MEAN = 2
+AGG_TOPMEAN = 3
 ALIGN_MAX_CELLS = 9216  # VSC_ALIGN_MAX_CELLS: lq * lr of the largest pair whose working state fits LDS
 
 # every symbol include/vscmi.h declares
@@ -46,7 +51,7 @@ EXPORTS = (
     "vsc_index_create", "vsc_index_create_codec", "vsc_index_destroy", "vsc_index_add", "vsc_index_add_f16", "vsc_index_reconstruct", "vsc_index_ntotal", "vsc_index_dim",
     "vsc_index_metric", "vsc_index_set_hit_capacity", "vsc_index_sync", "vsc_index_knn",
     "vsc_index_set_option", "vsc_index_get_option", "vsc_index_set_stream", "vsc_tn_set_stream", "vsc_set_aux_stream",
-    "vsc_index_range_search", "vsc_index_global_topk", "vsc_index_global_topk_seeded", "vsc_index_candidates", "vsc_pair_max", "vsc_sort_hits", "vsc_row_normalize",
+    "vsc_index_range_search", "vsc_index_global_topk", "vsc_index_global_topk_seeded", "vsc_index_candidates", "vsc_index_candidates_agg", "vsc_pair_max", "vsc_pair_aggregate", "vsc_sort_hits", "vsc_row_normalize",
     "vsc_score_histogram", "vsc_score_pick", "vsc_filter_hits", "vsc_argsort_scores", "vsc_merge_topk",
     "vsc_tn_create", "vsc_tn_create_codec", "vsc_tn_ref_bytes", "vsc_tn_set_queries", "vsc_tn_destroy", "vsc_tn_localize", "vsc_tn_forward_sim", "vsc_tn_similarity",
     "vsc_tn_align", "vsc_align_forward_sim", "vsc_tn_set_timestamps", "vsc_tn_match_rows", "vsc_match_metric",
@@ -190,6 +195,9 @@ def lib():
         L.vsc_index_candidates.argtypes = [vp, vp, i64, i32, i64, vp, vp, vp, vp, vp, i64, pi64, pi64]
         L.vsc_pair_max.argtypes = [vp, vp, vp, i64, i32, vp, i64, vp, i64, i32, vp, vp, vp, vp, i64,
                                    i32, pi64, i32]
+        L.vsc_pair_aggregate.argtypes = [vp, vp, vp, i64, i32, vp, i64, vp, i64, i32, i32, i32, i64, vp, vp, vp, vp, vp, i64,
+                                         i32, pi64, i32]
+        L.vsc_index_candidates_agg.argtypes = [vp, vp, i64, i32, i64, vp, vp, i32, i64, vp, vp, vp, i64, pi64, pi64]
         L.vsc_sort_hits.argtypes = [vp, vp, vp, i64, i32, i64, i64, vp, vp, vp, i32, i32]
         L.vsc_row_normalize.argtypes = [vp, i64, i32, i32, vp, i32, i32]
         L.vsc_score_histogram.argtypes = [vp, i64, vp, i32, vp, i32]

@@ -372,6 +372,7 @@ int vsc_index_destroy(vsc_index_t* idx) {
     idx->ref8m.release();
     idx->i8_mu.release();
     for (auto& b : idx->cand) b.release();
+    idx->cand_ids.release();
     idx->ws.release();
     for (auto& e : idx->ev_pool) {
         (void)hipEventDestroy(e.first);

@@ -1,4 +1,4 @@
-// C ABI of libvscmi.so, part 4: the entry points that own no index handle (vsc_pair_max, vsc_row_normalize, vsc_match_metric) and the
+// C ABI of libvscmi.so, part 4: the entry points that own no index handle (vsc_pair_max, vsc_pair_aggregate, vsc_row_normalize, vsc_match_metric) and the
 // Temporal-Network localisation contexts (vsc_tn_*), the DTW / DP aligners on them (vsc_tn_align, vsc_align_forward_sim)
 // and the match-rows stage behind both (vsc_tn_set_timestamps, vsc_tn_match_rows).
 #include "api_internal.h"
@@ -118,6 +118,78 @@ int vsc_pair_max(const int32_t* hit_i, const int32_t* hit_j, const float* hit_s,
     }
     VSC_HIP(hipStreamSynchronize(c->stream));
     tm.collect();
+    return VSC_OK;
+}
+
+int vsc_pair_aggregate(const int32_t* hit_i, const int32_t* hit_j, const float* hit_s, int64_t n, int hits_mem,
+                       const int32_t* row2q, int64_t nq_rows, const int32_t* row2r, int64_t nr_rows, int maps_mem,
+                       int hits_order, int agg, int64_t top_m, int32_t* out_q, int32_t* out_r, float* out_s,
+                       int64_t* out_first, int32_t* out_count, int64_t cap, int out_mem, int64_t* n_pairs, int device) {
+    // (the aggregation is judged first: a bad one is refused whatever else the call holds, with no device looked at)
+    VSC_TRY(pair_agg_check("vsc_pair_aggregate", agg, top_m));
+    if (n < 0 || n > 0x7fffffffLL || nq_rows < 0 || nr_rows < 0 || cap < 0 || !n_pairs ||
+        (n > 0 && (!hit_i || !hit_j || !hit_s || !row2q || !row2r || !out_q || !out_r || !out_s))) {
+        set_error("vsc_pair_aggregate: invalid argument");
+        return VSC_ERR_INVALID;
+    }
+    *n_pairs = 0;
+    if (n == 0) return VSC_OK;
+    if (hits_mem == VSC_MEM_HOST) {
+        for (int64_t x = 0; x < n; ++x) {
+            if (hit_i[x] < 0 || hit_i[x] >= nq_rows || hit_j[x] < 0 || hit_j[x] >= nr_rows) {
+                set_error("vsc_pair_aggregate: hit %lld names row (%d, %d) outside the row -> video maps (%lld query rows, %lld "
+                          "reference rows)", (long long)x, (int)hit_i[x], (int)hit_j[x], (long long)nq_rows, (long long)nr_rows);
+                return VSC_ERR_INVALID;
+            }
+        }
+    }
+    VSC_TRY(check_device(device));
+    VSC_HIP(hipSetDevice(device));
+    DeviceCtx* c = device_ctx(device);
+    if (!c) {
+        set_error("vsc_pair_aggregate: cannot create device context");
+        return VSC_ERR_HIP;
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    Workspace& ws = c->ws;
+    const void *di, *dj, *ds, *dq, *dr;
+    VSC_TRY(to_device(hit_i, (size_t)n * 4, hits_mem, ws.hA[0], &di, c->stream));
+    VSC_TRY(to_device(hit_j, (size_t)n * 4, hits_mem, ws.hA[1], &dj, c->stream));
+    VSC_TRY(to_device(hit_s, (size_t)n * 4, hits_mem, ws.hA[2], &ds, c->stream));
+    VSC_TRY(to_device(row2q, (size_t)nq_rows * 4, maps_mem, ws.maps0, &dq, c->stream));
+    VSC_TRY(to_device(row2r, (size_t)nr_rows * 4, maps_mem, ws.maps1, &dr, c->stream));
+    int32_t *oq = out_q, *orr = out_r, *oc = out_count;
+    float* os = out_s;
+    int64_t* of = out_first;
+    const int64_t ocap = out_mem == VSC_MEM_HOST ? n : cap;
+    if (out_mem == VSC_MEM_HOST) {
+        VSC_TRY(ws.out[0].reserve((size_t)n * 4));
+        VSC_TRY(ws.out[1].reserve((size_t)n * 4));
+        VSC_TRY(ws.out[2].reserve((size_t)n * 4));
+        VSC_TRY(ws.out[3].reserve((size_t)n * 8));
+        VSC_TRY(ws.parts.reserve((size_t)n * 4));
+        oq = ws.out[0].as<int32_t>();
+        orr = ws.out[1].as<int32_t>();
+        os = ws.out[2].as<float>();
+        of = ws.out[3].as<int64_t>();
+        oc = ws.parts.as<int32_t>();
+    }
+    int64_t np = 0;
+    VSC_TRY(pair_aggregate_device((const int32_t*)di, (const int32_t*)dj, (const float*)ds, n, (const int32_t*)dq, (const int32_t*)dr,
+                                  nq_rows, nr_rows, hits_order, agg, top_m, ws.sort, ws.agg, oq, orr, os, of, oc, ocap, &np, c->stream));
+    *n_pairs = np;
+    if (out_mem == VSC_MEM_HOST) {
+        if (np > cap) {
+            set_error("vsc_pair_aggregate: output capacity %lld < %lld pairs", (long long)cap, (long long)np);
+            return VSC_ERR_CAPACITY;
+        }
+        VSC_HIP(hipMemcpyAsync(out_q, oq, (size_t)np * 4, hipMemcpyDeviceToHost, c->stream));
+        VSC_HIP(hipMemcpyAsync(out_r, orr, (size_t)np * 4, hipMemcpyDeviceToHost, c->stream));
+        VSC_HIP(hipMemcpyAsync(out_s, os, (size_t)np * 4, hipMemcpyDeviceToHost, c->stream));
+        if (out_first) VSC_HIP(hipMemcpyAsync(out_first, of, (size_t)np * 8, hipMemcpyDeviceToHost, c->stream));
+        if (out_count) VSC_HIP(hipMemcpyAsync(out_count, oc, (size_t)np * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    VSC_HIP(hipStreamSynchronize(c->stream));
     return VSC_OK;
 }
 

@@ -24,6 +24,7 @@ struct Workspace {
     DevBuf hA[3], hB[3];  // kept hits (i, j, s) + compaction target
     DevBuf ctl;     // SelectCtl
     SortScratch sort;  // scratch of the radix sorts (sortpairs.hip)
+    PairAggScratch agg;  // ... and of the pair aggregation on top of them (pair_reduce.hip)
     DevBuf cnt;        // small counters read back by the host
     DevBuf out[4];  // device-side outputs when the caller wants host results
     DevBuf parts, partj, mat, maps0, maps1;
@@ -59,7 +60,7 @@ struct Workspace {
         for (auto& b : dd) b.release();
         for (auto& b : hA) b.release();
         for (auto& b : hB) b.release();
-        ctl.release(); sort.release(); cnt.release();
+        ctl.release(); sort.release(); agg.release(); cnt.release();
         for (auto& b : out) b.release();
         parts.release(); partj.release(); mat.release(); maps0.release(); maps1.release();
     }
@@ -179,6 +180,7 @@ struct vsc_index {
     double prefilter_density = 0.05;  // expected hit density below which a batch goes through the pre-filter (r03: 0.02 -> 0.05 with the cheaper exact stage: -0.8 %)
     unsigned long long stat_candidates = 0, stat_hits = 0;  // last search (vsc_index_profile_read)
     DevBuf cand[3];  // sorted hits of vsc_index_candidates
+    DevBuf cand_ids;  // the int64 ids of the k-NN form of vsc_index_candidates_agg
     hipStream_t stream = nullptr;      // the stream every launch of this handle goes to: own_stream, or the caller's
     hipStream_t own_stream = nullptr;  // (vsc_index_set_stream)
     int64_t cand_budget = (int64_t)1 << 28;  // cand_budget: entries of the candidate list a k-NN threshold pass may ask for

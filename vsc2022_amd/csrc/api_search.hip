@@ -882,6 +882,77 @@ int vsc_index_candidates(vsc_index_t* idx, const float* q, int64_t nq, int q_mem
     return VSC_OK;
 }
 
+int vsc_index_candidates_agg(vsc_index_t* idx, const float* q, int64_t nq, int q_mem, int64_t K, const int32_t* row2q,
+                             const int32_t* row2r, int agg, int64_t top_m, int32_t* out_q, int32_t* out_r, float* out_s,
+                             int64_t cap_out, int64_t* n_pairs, int64_t* n_hits) {
+    VSC_TRY(pair_agg_check("vsc_index_candidates_agg", agg, top_m));
+    if (!idx || nq < 0 || !n_pairs || cap_out < 0 || (nq > 0 && (!q || !row2q || !row2r))) {
+        set_error("vsc_index_candidates_agg: invalid argument");
+        return VSC_ERR_INVALID;
+    }
+    *n_pairs = 0;
+    if (n_hits) *n_hits = 0;
+    if (idx->metric != VSC_METRIC_INNER_PRODUCT) {
+        set_error("vsc_index_candidates_agg: the aggregations need a larger-is-better metric (inner product)");
+        return VSC_ERR_INVALID;
+    }
+    const bool knn = K < 0;
+    if (knn && (-K > idx->ntotal || -K > 0x7fffffffLL)) {
+        set_error("vsc_index_candidates_agg: k = %lld neighbours of %lld reference rows (an empty slot has no video)",
+                  (long long)-K, (long long)idx->ntotal);
+        return VSC_ERR_INVALID;
+    }
+    if (nq == 0 || idx->ntotal == 0 || K == 0) return VSC_OK;
+    VSC_HIP(hipSetDevice(idx->device));
+    // 1. the hits stay in HBM: the score-sorted top-K, or the (row, rank) lists of the k-NN
+    const int64_t hcap = knn ? nq * -K : std::max<int64_t>(1, std::min<int64_t>(K, nq * idx->ntotal));
+    if (hcap > 0x7fffffffLL) {
+        set_error("vsc_index_candidates_agg: %lld hits are beyond the supported size", (long long)hcap);
+        return VSC_ERR_INVALID;
+    }
+    for (int c = 0; c < 3; ++c) VSC_TRY(idx->cand[c].reserve((size_t)hcap * 4));
+    int64_t n = 0;
+    if (knn) {
+        const int k = (int)-K;
+        VSC_TRY(idx->cand_ids.reserve((size_t)hcap * 8));
+        VSC_TRY(vsc_index_knn(idx, q, nq, q_mem, k, idx->cand[2].as<float>(), idx->cand_ids.as<int64_t>(), VSC_MEM_DEVICE));
+        VSC_TRY(launch_knn_to_hits(idx->cand_ids.as<int64_t>(), nq, k, idx->cand[0].as<int32_t>(), idx->cand[1].as<int32_t>(), idx->stream));
+        n = hcap;
+    } else {
+        float radius = 0.0f;
+        VSC_TRY(vsc_index_global_topk(idx, q, nq, q_mem, K, idx->cand[0].as<int32_t>(), idx->cand[1].as<int32_t>(),
+                                      idx->cand[2].as<float>(), hcap, VSC_MEM_DEVICE, &n, &radius));
+    }
+    if (n_hits) *n_hits = n;
+    if (n == 0) return VSC_OK;
+    // 2. the (query video, ref video) aggregation on the device
+    Workspace& ws = idx->ws;
+    VSC_TRY(ws.maps0.reserve((size_t)nq * 4));
+    VSC_TRY(ws.maps1.reserve((size_t)idx->ntotal * 4));
+    VSC_HIP(hipMemcpyAsync(ws.maps0.p, row2q, (size_t)nq * 4, hipMemcpyHostToDevice, idx->stream));
+    VSC_HIP(hipMemcpyAsync(ws.maps1.p, row2r, (size_t)idx->ntotal * 4, hipMemcpyHostToDevice, idx->stream));
+    for (int c = 0; c < 3; ++c) VSC_TRY(ws.out[c].reserve((size_t)n * 4));
+    int64_t np = 0;
+    VSC_TRY(pair_aggregate_device(idx->cand[0].as<int32_t>(), idx->cand[1].as<int32_t>(), idx->cand[2].as<float>(), n,
+                                  ws.maps0.as<int32_t>(), ws.maps1.as<int32_t>(), nq, idx->ntotal, knn ? 0 : 1, agg, top_m, ws.sort,
+                                  ws.agg, ws.out[0].as<int32_t>(), ws.out[1].as<int32_t>(), ws.out[2].as<float>(), nullptr, nullptr,
+                                  n, &np, idx->stream));
+    *n_pairs = np;
+    if (np > cap_out) {
+        set_error("vsc_index_candidates_agg: output capacity %lld < %lld pairs", (long long)cap_out, (long long)np);
+        return VSC_ERR_CAPACITY;
+    }
+    if (np > 0 && (!out_q || !out_r || !out_s)) {
+        set_error("vsc_index_candidates_agg: invalid argument (no output arrays)");
+        return VSC_ERR_INVALID;
+    }
+    VSC_HIP(hipMemcpyAsync(out_q, ws.out[0].p, (size_t)np * 4, hipMemcpyDeviceToHost, idx->stream));
+    VSC_HIP(hipMemcpyAsync(out_r, ws.out[1].p, (size_t)np * 4, hipMemcpyDeviceToHost, idx->stream));
+    VSC_HIP(hipMemcpyAsync(out_s, ws.out[2].p, (size_t)np * 4, hipMemcpyDeviceToHost, idx->stream));
+    VSC_HIP(hipStreamSynchronize(idx->stream));
+    return VSC_OK;
+}
+
 int vsc_index_range_search(vsc_index_t* idx, const float* q, int64_t nq, int q_mem, float radius,
                            int64_t* lims, float* D, int64_t* I, int64_t cap_out, int64_t* n_out) {
     if (!idx || nq < 0 || !lims || !n_out || (nq > 0 && !q)) {

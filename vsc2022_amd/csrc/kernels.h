@@ -11,6 +11,12 @@ struct SortScratch {
     DevBuf w0, w1, w2, w3, tmp;
     void release() { w0.release(); w1.release(); w2.release(); w3.release(); tmp.release(); }
 };
+// Scratch of the pair aggregation beyond the sorts' (pair_reduce.hip): the per-pair results, the final sort's ping-pong
+// buffers and the control words.
+struct PairAggScratch {
+    DevBuf k2, v2a, v2b, rs, rfirst, rcnt, ctl;
+    void release() { k2.release(); v2a.release(); v2b.release(); rs.release(); rfirst.release(); rcnt.release(); ctl.release(); }
+};
 // A hit list on the device: (row, ref, score) in three parallel arrays.
 struct HitView { int32_t* i; int32_t* j; float* s; };
 struct ConstHitView {
@@ -316,6 +322,13 @@ int sort_hits_topk(ConstHitView, int64_t, int64_t, int64_t, int64_t, SortScratch
 int sort_hits_rowcol(ConstHitView, int64_t, SortScratch&, HitView, int, hipStream_t);
 int pair_max_device(const int32_t*, const int32_t*, const float*, int64_t, const int32_t*, const int32_t*, int64_t, int64_t,
                     SortScratch&, DevBuf&, int32_t*, int32_t*, float*, int64_t*, int64_t, int64_t*, hipStream_t);
+// pair_reduce.hip: max / sum / mean / top-m mean per (query video, ref video), pairs in their final order
+int pair_agg_check(const char* who, int agg, int64_t top_m);
+int pair_aggregate_device(const int32_t* hi, const int32_t* hj, const float* hs, int64_t n, const int32_t* row2q, const int32_t* row2r,
+                          int64_t nq_rows, int64_t nr_rows, int hits_order, int agg, int64_t top_m, SortScratch&, PairAggScratch&,
+                          int32_t* out_q, int32_t* out_r, float* out_s, int64_t* out_first, int32_t* out_count, int64_t cap,
+                          int64_t* n_pairs, hipStream_t);
+int launch_knn_to_hits(const int64_t* ids, int64_t nq, int k, int32_t* hi, int32_t* hj, hipStream_t);
 int launch_pack_rows(const float*, int64_t, int, float*, int64_t, int, hipStream_t);
 int launch_row_normalize(const float*, int64_t, int, float*, hipStream_t);
 size_t tn_state_bytes_host(int, int, int, int idx_bytes = 2);

@@ -56,6 +56,27 @@ class MatchResult:
     row_boxes: Optional[torch.Tensor] = None   # [n_rows, 4] int32 q_lo, r_lo, q_hi, r_hi
 
 
+_AGG_NAMES = {"max": _lib.AGG_MAX, "sum": _lib.AGG_SUM, "mean": _lib.AGG_MEAN, "topmean": _lib.AGG_TOPMEAN}
+
+
+def aggregation_id(aggregation, top_m: int = 1):
+    """(VSC_AGG_* id, top_m) of "max" | "sum" | "mean" | ("topmean", m), or of an id with its top_m; ValueError for
+    anything else (before the library is called)."""
+    if isinstance(aggregation, (tuple, list)):
+        if len(aggregation) != 2 or aggregation[0] != "topmean":
+            raise ValueError(f"aggregation {aggregation!r}: the only parametrised one is ('topmean', m)")
+        aggregation, top_m = "topmean", aggregation[1]
+    if isinstance(aggregation, str):
+        if aggregation not in _AGG_NAMES:
+            raise ValueError(f"aggregation {aggregation!r}: 'max', 'sum', 'mean' or ('topmean', m)")
+        aggregation = _AGG_NAMES[aggregation]
+    if aggregation not in _AGG_NAMES.values():
+        raise ValueError(f"aggregation id {aggregation!r}: one of VSC_AGG_MAX, _SUM, _MEAN, _TOPMEAN")
+    if aggregation == _lib.AGG_TOPMEAN and (int(top_m) != top_m or top_m < 1):
+        raise ValueError(f"('topmean', m) needs an integer m >= 1, got {top_m!r}")
+    return int(aggregation), int(top_m)
+
+
 def _dev_ptr(t: torch.Tensor) -> int:
     assert t.is_cuda and t.is_contiguous()
     return t.data_ptr()
@@ -355,6 +376,29 @@ class DeviceMatcher:
         m = n_pairs.value
         return oq[:m], orr[:m], os_[:m], of[:m]
 
+    def pair_aggregate(self, hi, hj, hs, agg, top_m: int = 1, hits_order: int = 1):
+        """The same regroup with a choice of aggregation (include/vscmi.h, vsc_pair_aggregate): agg is "max", "sum",
+        "mean", ("topmean", m) or a VSC_AGG_* id with top_m.  hits_order: 1 = the list is in search order (score
+        descending), 0 = any order.  Returns (q, r, score, first hit, hit count) in the final candidate order."""
+        agg, top_m = aggregation_id(agg, top_m)
+        n = int(hs.numel())
+        oq = self._buf("agg_q", max(n, 1), torch.int32)
+        orr = self._buf("agg_r", max(n, 1), torch.int32)
+        os_ = self._buf("agg_s", max(n, 1), torch.float32)
+        of = self._buf("agg_f", max(n, 1), torch.int64)
+        oc = self._buf("agg_c", max(n, 1), torch.int32)
+        n_pairs = ctypes.c_int64(0)
+        if n:
+            hi, hj, hs = hi.contiguous(), hj.contiguous(), hs.contiguous()
+            self._order()
+            _lib.check(_lib.lib().vsc_pair_aggregate(
+                _dev_ptr(hi), _dev_ptr(hj), _dev_ptr(hs), n, _lib.MEM_DEVICE, _dev_ptr(self.row2q),
+                int(self.row2q.numel()), _dev_ptr(self.row2r), int(self.row2r.numel()), _lib.MEM_DEVICE,
+                int(hits_order), agg, top_m, _dev_ptr(oq), _dev_ptr(orr), _dev_ptr(os_), _dev_ptr(of), _dev_ptr(oc), n,
+                _lib.MEM_DEVICE, ctypes.byref(n_pairs), self.device))
+        m = n_pairs.value
+        return oq[:m], orr[:m], os_[:m], of[:m], oc[:m]
+
     def localize(self, pair_q: torch.Tensor, pair_r: torch.Tensor, bias: float = 0.0, **tn_kwargs):
         """vsc/baseline/localization.py:56-96 for device-resident pair lists (LOCAL query ordinals)."""
         n = int(pair_q.numel())
@@ -372,7 +416,8 @@ class DeviceMatcher:
 
     # ---- the whole hot path
     def match(self, n_qvid_global: Optional[int] = None, qvid_base: int = 0, row_base: int = 0, group=None,
-              bias: float = 0.0, localize: bool = True, rows: bool = False, box_score: str = "maxsim") -> MatchResult:
+              bias: float = 0.0, localize: bool = True, rows: bool = False, box_score: str = "maxsim",
+              aggregation="max") -> MatchResult:
         """search -> candidates -> localisation for the resident queries.
 
         Single process: n_qvid_global is None.  Sharded (one process per GPU): this rank owns the
@@ -383,7 +428,10 @@ class DeviceMatcher:
         process localised (MatchResult.row_*: candidate index, video ordinals, score, the four timestamps), made on the
         device from the box table and the timestamps given to the constructor / `set_queries`; `match_table` turns them
         into a MatchTable.  box_score: "maxsim" (the kernel's box score) or "candidate" (the candidate's score).
+        aggregation: how a pair's hit scores become the candidate's score -- "max" (the reference's, `pair_max`), "sum",
+        "mean" or ("topmean", m) (`pair_aggregate`); single process only: merging sums across ranks is not defined here.
         """
+        agg, top_m = aggregation_id(aggregation)
         if box_score not in ("maxsim", "candidate"):
             raise ValueError(f"box_score {box_score!r}: 'maxsim' or 'candidate'")
         if rows and (getattr(self, "_q_ts", None) is None or getattr(self, "_r_ts", None) is None):
@@ -391,6 +439,8 @@ class DeviceMatcher:
                              "set_queries(..., q_ts=...)")
         sharded = n_qvid_global is not None and torch.distributed.is_initialized() and \
             (torch.distributed.get_world_size(group) > 1 or os.environ.get("VSC_FORCE_SHARDED") == "1")
+        if sharded and agg != _lib.AGG_MAX:
+            raise ValueError(f"match(aggregation={aggregation!r}): a sharded run aggregates by \"max\" only")
         nq_glob = n_qvid_global if n_qvid_global is not None else self.n_qvid
         K = int(RETRIEVE_PER_QUERY * nq_glob)
         n_cand_cut = int(CANDIDATES_PER_QUERY * nq_glob)
@@ -398,7 +448,10 @@ class DeviceMatcher:
         if not sharded:
             hi, hj, hs, radius = self.search(K)
             self.last_hits = (hi, hj, hs)   # (views of the search's output buffers: valid until the next search)
-            pq, pr, ps, pf = self.pair_max(hi, hj, hs)
+            if agg == _lib.AGG_MAX:
+                pq, pr, ps, pf = self.pair_max(hi, hj, hs)
+            else:
+                pq, pr, ps, pf, _ = self.pair_aggregate(hi, hj, hs, agg, top_m, hits_order=1)
             n_cand = min(int(ps.numel()), n_cand_cut)
             n_loc = min(n_cand, n_loc_cut) if localize else 0
             nbox, boxes, bmax = self.localize(pq[:n_loc], pr[:n_loc], bias)

@@ -20,6 +20,14 @@ METRIC_L2 = _lib.METRIC_L2
 
 SearchIndices = Tuple[int, int, float]
 
+# vsc/index.py:109-114: logged by every k-NN retrieval (global_k < 0)
+KNN_WARNING = (
+    "Using local k for KNN search. Warning: this is against the "
+    "VSC rules, since predictions for a query-ref pair are not "
+    "independent of other references. KNN search is provided for "
+    "comparison."
+)
+
 
 @dataclass
 class VideoMetadata:
@@ -479,12 +487,7 @@ class VideoIndex:
         feats = VideoLayout.features(queries)
         if global_k < 0:
             k = -global_k
-            logging.warning(
-                "Using local k for KNN search. Warning: this is against the "
-                "VSC rules, since predictions for a query-ref pair are not "
-                "independent of other references. KNN search is provided for "
-                "comparison."
-            )
+            logging.warning(KNN_WARNING)
             D, I = self.index.search(feats, k)  # vsc/index.py:167-177: (row, rank) order
             i = np.repeat(np.arange(D.shape[0], dtype=np.int32), k)
             return SearchHits(i, I.reshape(-1).astype(np.int32), D.reshape(-1), layout, self)
