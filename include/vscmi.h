@@ -364,10 +364,16 @@ int vsc_row_normalize(const float* x, int64_t n, int dim, int x_mem, float* out,
  * offsets per query video; same for refs. */
 typedef struct vsc_tn_ctx vsc_tn_ctx_t;
 
+/* Supported ranges (anything else is VSC_ERR_INVALID): tn_top_k 1..16, tn_max_step 1..64, max_path 0..15
+ * (max_path + 1 extractions fill at most the VSC_TN_MAX_BOXES = 16 boxes of a pair).  min_length, min_sim and max_iou
+ * are unrestricted: a min_sim below every score admits every edge, max_iou <= 0 keeps the first box only, max_iou > 1
+ * keeps every one.  Every combination in range runs for every video length; the working state of a pair grows with
+ * tn_top_k^2 * tn_max_step per query frame, and pairs whose state or similarity tile do not fit the LDS of a launch
+ * run from HBM with identical results. */
 typedef struct vsc_tn_params {
-    int32_t tn_max_step; /* VCSL default 10; reference passes 5 (sscd_baseline.py:122,132) */
-    int32_t tn_top_k;    /* 5 */
-    int32_t max_path;    /* 10 */
+    int32_t tn_max_step; /* 1..64; VCSL default 10; reference passes 5 (sscd_baseline.py:122,132) */
+    int32_t tn_top_k;    /* 1..16; 5 */
+    int32_t max_path;    /* 0..15; 10 */
     int32_t min_length;  /* VCSL default 5; reference passes 4 */
     float min_sim;       /* 0.2 */
     float max_iou;       /* 0.3 */

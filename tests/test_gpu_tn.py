@@ -2,6 +2,8 @@
 import numpy as np
 import pytest
 
+from tn_cases import rand_sims  # (the generator moved there unchanged: the same 400 matrices)
+
 pytestmark = pytest.mark.gpu
 
 
@@ -12,28 +14,6 @@ def unit(rng, n, d):
 
 def bits(x):
     return np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
-
-
-def rand_sims(rng, trial):
-    lq = int(rng.integers(1, 70))
-    lr = int(rng.integers(1, 90))
-    mode = trial % 6
-    sims = rng.normal(0, 0.12, size=(lq, lr)).astype(np.float32)
-    if mode in (1, 3, 5):
-        for _ in range(rng.integers(1, 4)):
-            L = int(rng.integers(3, 30))
-            q0 = int(rng.integers(0, max(1, lq - 2)))
-            r0 = int(rng.integers(0, max(1, lr - 2)))
-            for t in range(L):
-                if q0 + t < lq and r0 + t < lr:
-                    sims[q0 + t, r0 + t] = 0.8 + 0.2 * rng.random()
-    if mode in (2, 3):
-        sims = np.round(sims * 4) / 4
-    if mode == 4:
-        sims += 0.5
-    if mode == 5:
-        sims = np.round(sims * 8) / 8 + 0.5
-    return sims.astype(np.float32)
 
 
 @pytest.mark.parametrize("kw", [{}, dict(tn_max_step=5, min_length=4),

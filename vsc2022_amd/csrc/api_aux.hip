@@ -432,6 +432,12 @@ static int tn_run_buckets(TnPairArgs base, const std::vector<int32_t>& lqs, cons
     constexpr int64_t BIG_CHUNK_BYTES = (int64_t)4 << 30;  // state + similarity slab of one launch of the HBM route
     struct Bucket { int max_lq; int64_t max_tile; std::vector<int32_t> work; int seen_lq; int64_t seen_tile; };
     Bucket buckets[4] = {{64, 4096, {}, 0, 0}, {256, 24576, {}, 0, 0}, {0x7fffffff, 0, {}, 0, 0}, {0x7fffffff, 0, {}, 0, 0}};
+    // The state grows with top^2 * step: an LDS-tile bucket (fused route) takes pairs only when the state of its
+    // longest video plus its largest tile fit one launch.  Otherwise its pairs go to the slab bucket -- same results.
+    // (Both fit at the default and the reference's parameters: 143 488 and 134 336 bytes for bucket 1.)
+    bool tile_ok[2];
+    for (int b = 0; b < 2; ++b)
+        tile_ok[b] = tn_state_bytes_host(buckets[b].max_lq, topc, ms) + (size_t)buckets[b].max_tile * 4 <= TN_LAUNCH_LDS_MAX;
     for (int64_t p = 0; p < n_pairs; ++p) {
         const int64_t lq = lqs[(size_t)p], lr = lrs[(size_t)p];
         if (lq * std::max<int64_t>(1, topc) * ms * topc > 0x7fff0000LL || lq * lr > ((int64_t)1 << 40)) {
@@ -440,8 +446,8 @@ static int tn_run_buckets(TnPairArgs base, const std::vector<int32_t>& lqs, cons
         }
         int b = 2;
         if (lq * topc + 1 > 32767 || lr > 32767 || tn_state_bytes_host((int)std::max<int64_t>(lq, 1), topc, ms) > LDS_STATE_MAX) b = 3;
-        else if (lq <= 64 && (!fused || lq * lr <= 4096)) b = 0;
-        else if (lq <= 256 && (!fused || lq * lr <= 24576)) b = 1;
+        else if (lq <= 64 && (!fused || (tile_ok[0] && lq * lr <= 4096))) b = 0;
+        else if (lq <= 256 && (!fused || (tile_ok[1] && lq * lr <= 24576))) b = 1;
         buckets[b].work.push_back((int32_t)p);
         buckets[b].seen_lq = std::max<int>(buckets[b].seen_lq, (int)lq);
         buckets[b].seen_tile = std::max<int64_t>(buckets[b].seen_tile, lq * lr);

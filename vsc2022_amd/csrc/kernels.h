@@ -331,6 +331,9 @@ int pair_aggregate_device(const int32_t* hi, const int32_t* hj, const float* hs,
 int launch_knn_to_hits(const int64_t* ids, int64_t nq, int k, int32_t* hi, int32_t* hj, hipStream_t);
 int launch_pack_rows(const float*, int64_t, int, float*, int64_t, int, hipStream_t);
 int launch_row_normalize(const float*, int64_t, int, float*, hipStream_t);
+// dynamic LDS a tn_pair_kernel launch may ask for (working state + similarity tile): what launch_tn_pairs sets as the
+// kernel's limit and what tn_run_buckets plans its LDS-tile buckets against (a workgroup has 160 KiB on gfx950)
+constexpr size_t TN_LAUNCH_LDS_MAX = 158 * 1024;
 size_t tn_state_bytes_host(int, int, int, int idx_bytes = 2);
 int launch_tn_pairs(const TnPairArgs&, size_t, hipStream_t);
 int launch_tn_sims(const TnSimsArgs&, hipStream_t);

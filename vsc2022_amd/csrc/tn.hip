@@ -682,8 +682,12 @@ static int launch_tn_pairs_from(const TnPairArgs& a, size_t lds_bytes, hipStream
     }
     if (once.first()) {
         VSC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&tn_pair_kernel<short, false, RH16>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)TN_LAUNCH_LDS_MAX));
         once.commit();
+    }
+    if (lds_bytes > TN_LAUNCH_LDS_MAX) {  // (tn_run_buckets plans inside the limit: a launch beyond it would be refused)
+        set_error("TN: a launch of %zu bytes of LDS is beyond the limit of %zu", lds_bytes, TN_LAUNCH_LDS_MAX);
+        return VSC_ERR_INVALID;
     }
     hipLaunchKernelGGL((tn_pair_kernel<short, false, RH16>), dim3((unsigned)a.n_work), dim3(64), lds_bytes, stream, a);
     VSC_HIP(hipGetLastError());
