@@ -178,7 +178,9 @@ int64_t vsc_index_ntotal(const vsc_index_t* idx);
 int vsc_index_dim(const vsc_index_t* idx);
 int vsc_index_metric(const vsc_index_t* idx);
 /* Capacity (entries) of the internal kept-hit buffer used by vsc_index_global_topk; 0 restores the
- * default max(32*ntotal, 2K) + 2K.  A search that overflows it returns VSC_ERR_OVERFLOW. */
+ * default max(32*ntotal, 2K) + 2K.  A search that overflows it returns VSC_ERR_OVERFLOW.  With the default, a search
+ * that overflows is rerun with four times the entries and the handle starts its later searches there: read-only option
+ * "hit_cap_learned" (entries; 0 while no search of the handle was rerun). */
 int vsc_index_set_hit_capacity(vsc_index_t* idx, int64_t cap);
 /* block until all work queued on the handle's stream has finished */
 int vsc_index_sync(vsc_index_t* idx);

@@ -207,3 +207,66 @@ def full_segment_capacity(nq, nr, ring, tile_cands, n_hits):
         shift += 1
     assert tail_cap >= 3 * cap and tail_cap >= n_hits + 2 * (1 << shift), "the candidates would not fit the tail"
     return cap
+
+
+# ---- vsc_match_metric: one call with canaries, and the checks every case of tests/test_gpu_match_metric.py gets
+
+METRIC_CANARY = -7.25
+
+
+def match_metric_table_result(gt, pred):
+    """(ap, precisions, recalls, scores) of the table route."""
+    from vsc2022_amd.vsc import metrics as M
+
+    res = M.match_metric_table(gt, pred)
+    return (res.ap, res.pr_curve.precisions, res.pr_curve.recalls, res.pr_curve.scores)
+
+
+def match_metric_raw(gt, pred, device_mem=False, cap=None, slack=3, spoil=None):
+    """One vsc_match_metric call with the tables in host memory or in HBM; outputs pre-filled with canaries.
+    Returns (rc, n_groups, scores, sums, gt_len, stats)."""
+    import ctypes
+
+    import match_metric_ref as mm
+    from vsc2022_amd import _lib
+
+    gp, pp, n_pairs, n_gt_pairs = mm.pair_ordinals(gt, pred)
+    ins = [gp, mm.times_of(gt), pp, np.asarray(pred.score, dtype=np.float64).copy(), mm.times_of(pred)]
+    if spoil:
+        spoil(ins)
+    ins = [np.ascontiguousarray(a) for a in ins]
+    cap = len(pred) if cap is None else cap
+    scores, sums = np.full(cap + slack, METRIC_CANARY), np.full((cap + slack, 4), METRIC_CANARY)
+    gt_len, stats, n_groups = np.zeros(2), np.zeros(8, dtype=np.int64), ctypes.c_int64(-1)
+    if device_mem:
+        import torch
+
+        keep = [torch.from_numpy(a).to("cuda:0") for a in ins]
+        torch.cuda.synchronize()
+        ptrs, mem = [t.data_ptr() if t.numel() else None for t in keep], _lib.MEM_DEVICE
+    else:
+        ptrs, mem = [a.ctypes.data for a in ins], _lib.MEM_HOST
+    rc = _lib.lib().vsc_match_metric(ptrs[0], ptrs[1], len(gt), None, n_gt_pairs, mem, ptrs[2], ptrs[3], ptrs[4], len(pred), mem,
+                                     n_pairs, scores.ctypes.data, sums.ctypes.data, cap, ctypes.byref(n_groups),
+                                     gt_len.ctypes.data, stats.ctypes.data, 0)
+    return rc, n_groups.value, scores, sums, gt_len, stats
+
+
+def check_match_metric_case(gt, pred, want_hbm=False, restatement=True):
+    """The raw sums are the restatement's, the table route is match_metric; returns the host AP."""
+    import match_metric_ref as mm
+    from vsc2022_amd import _lib
+
+    gp, pp, n_pairs, n_gt_pairs = mm.pair_ordinals(gt, pred)
+    rc, n_groups, scores, sums, gt_len, stats = match_metric_raw(gt, pred)
+    assert rc == _lib.VSC_OK, _lib.lib().vsc_last_error()
+    if restatement:
+        ref = mm.group_sums(gp, mm.times_of(gt), pp, pred.score, mm.times_of(pred), n_pairs, n_gt_pairs)
+        assert n_groups == len(ref[0])
+        assert np.array_equal(scores[:n_groups], ref[0]) and np.array_equal(sums[:n_groups], ref[1]) and np.array_equal(gt_len, ref[2])
+    assert (scores[n_groups:] == METRIC_CANARY).all() and (sums[n_groups:] == METRIC_CANARY).all()
+    assert stats[2] == len(pred) and stats[3] == n_groups and stats[0] + stats[1] == n_pairs
+    assert (stats[1] >= 1) if want_hbm else (stats[1] == 0), stats
+    want = mm.host_metric(gt, pred)  # (raises nowhere: the families' lengths see to that; a raise fails the test)
+    assert mm.same(match_metric_table_result(gt, pred), want)
+    return want[0]

@@ -16,65 +16,19 @@ import numpy as np
 import pytest
 
 from helpers import bits, load, videos
-from pair_agg_ref import pair_aggregate_ref
+from pair_agg_ref import CASES, pair_aggregate_ref
+from pair_agg_ref import assert_columns as _assert_columns
+from pair_agg_ref import case as _case
 
 pytestmark = pytest.mark.gpu
 
 AGGS = [("max", 1), ("sum", 1), ("mean", 1), ("topmean", 2), ("topmean", 65), ("topmean", 66)]
-ROWS_PER_VIDEO = 3
 
 
 def _agg_id(name):
     from vsc2022_amd import _lib
 
     return {"max": _lib.AGG_MAX, "sum": _lib.AGG_SUM, "mean": _lib.AGG_MEAN, "topmean": _lib.AGG_TOPMEAN}[name]
-
-
-def _hits(runs, seed):
-    """runs: [(q video, r video, scores)] -> (i, j, s, row2q, row2r) in SEARCH order (score desc, row asc, ref asc);
-    every video has ROWS_PER_VIDEO rows and a hit picks one of them at random."""
-    rng = np.random.default_rng(seed)
-    nqv = max(q for q, _, _ in runs) + 1
-    nrv = max(r for _, r, _ in runs) + 1
-    row2q = np.repeat(np.arange(nqv, dtype=np.int32), ROWS_PER_VIDEO)
-    row2r = np.repeat(np.arange(nrv, dtype=np.int32), ROWS_PER_VIDEO)
-    i = np.concatenate([q * ROWS_PER_VIDEO + rng.integers(0, ROWS_PER_VIDEO, len(sc)) for q, _, sc in runs]).astype(np.int32)
-    j = np.concatenate([r * ROWS_PER_VIDEO + rng.integers(0, ROWS_PER_VIDEO, len(sc)) for _, r, sc in runs]).astype(np.int32)
-    s = np.concatenate([np.asarray(sc, dtype=np.float32) for _, _, sc in runs])
-    order = np.lexsort((j, i, -s.astype(np.float64)))
-    return i[order], j[order], s[order], row2q, row2r
-
-
-def _case(name):
-    rng = np.random.default_rng(100 + CASES.index(name))
-    if name == "one_hit":
-        runs = [(2, 1, [0.5])]
-    elif name == "one_pair":
-        runs = [(0, 0, rng.standard_normal(5000))]
-    elif name == "run_lengths":
-        # pairs in key order (q ascending): the sorted runs start at 0, 1, 64, 128, 193, 448, 704, 961 -- the runs of 256,
-        # 257 and 1000 hits each lie across a multiple of 256 (checked below)
-        lens = [1, 63, 64, 65, 255, 256, 257, 1000, 1, 63, 64, 65, 255, 256, 257, 1000]
-        runs = [(q, int(rng.integers(0, 5)), rng.standard_normal(n)) for q, n in enumerate(lens)]
-        starts = np.r_[0, np.cumsum(lens)]
-        assert any(a // 256 != (b - 1) // 256 and a % 256 for a, b in zip(starts[:-1], starts[1:]))
-    elif name == "distinct":
-        pairs = rng.permutation(70 * 60)[:3000]
-        runs = [(int(p // 60), int(p % 60), [v]) for p, v in zip(pairs, rng.standard_normal(3000))]
-    elif name == "quantised":
-        pair = rng.integers(0, 600, 20000)
-        sc = rng.integers(-4, 5, 20000) / 8.0
-        runs = [(int(p // 25), int(p % 25), sc[pair == p]) for p in np.unique(pair)]
-    elif name == "order_revealing":
-        runs = [(int(p // 8), int(p % 8), rng.standard_normal(int(rng.integers(1, 40)))) for p in range(50)]
-        runs += [(7, 0, [2.0 ** 53] + [1.0] * 64 + [-(2.0 ** 53)]), (7, 1, [1e30, -1e30, 1.0]),
-                 (7, 2, [2.0 ** 53] + [1.0] * 300 + [-(2.0 ** 53)]), (7, 3, [1.0, 1e30, -1e30, 0.25])]
-    else:
-        raise KeyError(name)
-    return _hits(runs, len(name))
-
-
-CASES = ["one_hit", "one_pair", "run_lengths", "distinct", "quantised", "order_revealing"]
 
 
 def _device_call(i, j, s, row2q, row2r, agg, m, hits_order, device_mem):
@@ -102,17 +56,6 @@ def _device_call(i, j, s, row2q, row2r, agg, m, hits_order, device_mem):
                                              hits_order, _agg_id(agg), m, *optr, n, mem, ctypes.byref(n_pairs), 0))
     k = n_pairs.value
     return tuple((a.cpu().numpy() if device_mem else a)[:k] for a in out)
-
-
-def _assert_columns(got, exp, what):
-    names = ("q", "r", "score", "first", "count")
-    assert len(got[0]) == len(exp[0]), (what, len(got[0]), len(exp[0]))
-    for name, g, e in zip(names, got, exp):
-        if name == "score":
-            bad = np.flatnonzero(bits(g) != bits(e))
-        else:
-            bad = np.flatnonzero(g != e)
-        assert len(bad) == 0, (what, name, len(bad), bad[:5].tolist(), g[bad[:5]].tolist(), e[bad[:5]].tolist())
 
 
 @pytest.mark.parametrize("hits_order", [1, 0])

@@ -33,6 +33,47 @@ def test_parity_suites_with_poisoned_allocations():
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
 
 
+_PARITY = ["tests/test_gpu_search.py", "tests/test_gpu_edge_cases.py", "tests/test_gpu_golden.py", "-k", "not rccl_world1"]
+_FORCED_F16 = dict(VSC_PREFILTER="2", VSC_I8="0", VSC_TEST_QUICK="1")
+_FORCED_I8 = dict(VSC_PREFILTER="2", VSC_I8="2", VSC_I8_CENTER="2", VSC_TEST_QUICK="1")
+# family -> (route switches, pytest arguments): per kernel the smallest oracle-checked cases, nothing at full size and no
+# test that starts a process of its own (profiles/stale_memory.md holds each family's time against the run above)
+POISONED_FAMILIES = {
+    "fp16-panel": (_FORCED_F16, _PARITY),
+    "fp16-ring": (dict(_FORCED_F16, VSC_F16_KERNEL="ring"), _PARITY),
+    "int8": (_FORCED_I8, _PARITY),
+    "int8-screen-deferral": (dict(_FORCED_I8, VSC_I8_SCREEN="1", VSC_DEFER="2"),
+                             ["tests/test_gpu_search.py", "tests/test_gpu_defer.py", "-k",
+                              "test_gpu_search or forced_deferral or ties_on_radius"]),
+    "codec": ({}, ["tests/test_gpu_codec.py", "-k", "every_route_equals_flat or store_holds_dec"]),
+    "candidates": ({}, ["tests/test_gpu_pair_agg.py", "tests/test_gpu_search.py", "-k", "every_column or pair_max"]),
+    "localisation": ({}, ["tests/test_gpu_tn_params.py", "tests/test_gpu_tn_codec.py", "-k",
+                          "not (bytes_halve or cannot_hold or classes_take_ref_codec or out_of_range or Flat-0.0)"]),
+    "aligners-rows-metric": ({}, ["tests/test_gpu_aligners_device.py", "tests/test_gpu_match_rows.py", "tests/test_gpu_match_metric.py",
+                                  "-k", "host_function or thin_pairs or test_gpu_match_rows or coarse or lds_budget"]),
+    "select-abi": ({}, ["tests/test_gpu_select_abi.py"]),
+    # (one matcher over several query sets with half-float references only: with both codecs the file takes longer than the
+    # run above, and the localisation family runs the Flat context under poison)
+    "lifetime": ({}, ["tests/test_gpu_lifetime.py", "-k", "not (l5_one_matcher and Flat)"]),
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("family", list(POISONED_FAMILIES))
+def test_kernel_families_with_poisoned_allocations(family):
+    """The run above keeps to the default routes, which at its sizes is the exact fp32 kernel.  Here, under the same
+    VSC_POISON_ALLOC=1: the fp16 panel and ring pre-filters, the int8 pre-filter, the fp16 screen, the exact stage with its
+    candidate lists (shared tail and deferred set included), the SQfp16 store and its decoded ranges, the candidate
+    aggregation, the Temporal Network's HBM state and half-float references, the aligners, the match rows, the segment
+    AP, the scratch of the selection entry points -- and tests/test_gpu_lifetime.py, where handles are reused.  An
+    unwritten index reads as -1 and an unwritten score as NaN: a reader of memory nobody wrote fails its parity test."""
+    switches, args = POISONED_FAMILIES[family]
+    env = dict(os.environ, VSC_POISON_ALLOC="1", **switches)
+    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu"] + args, cwd=ROOT, env=env, capture_output=True,
+                       text=True, timeout=1200)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+
+
 @pytest.mark.gpu
 def test_overflow_retry_in_fresh_process():
     """First search of the process overflows the default kept-hit buffer and is rerun with a larger

@@ -268,6 +268,8 @@ static int read_option(const vsc_index* idx, const char* name, double* out) {
     else if (is("i8_center_on")) *out = idx->i8_mu_on;        // (read-only: is the int8 reference image centred?)
     else if (is("i8_center_share")) *out = idx->i8_mu_ratio;  // (read-only: |mean|^2 / mean |row|^2 when it was decided)
     else if (is("i8_fallbacks")) *out = (double)idx->stat_i8_fallbacks;  // (read-only: searches that left int8 for fp16)
+    // (read-only: the kept-hit capacity the last overflow rerun of vsc_index_global_topk ended with; 0: none happened)
+    else if (is("hit_cap_learned")) *out = (double)idx->hit_cap_learned;
     else if (is("codec")) *out = idx->codec;  // (read-only: VSC_CODEC_FLAT / VSC_CODEC_SQFP16, fixed at creation)
     // (read-only: bytes allocated for reference images of all kinds -- store, pre-filter images, per-row tables)
     else if (is("ref_bytes")) *out = (double)(idx->ref.bytes + idx->refh.bytes + idx->refn.bytes + idx->ref8.bytes + idx->ref8m.bytes);
