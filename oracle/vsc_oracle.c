@@ -481,8 +481,8 @@ int orc_global_threshold_search(const float *q, int64_t nq, const float *r, int6
 /*
  * faiss index.search(x, k) as used by VideoIndex._knn_search (vsc/index.py:167-177) and
  * score_normalize (vsc/baseline/score_normalization.py:96).  Per row the k best refs ordered
- * by (score desc, ref asc) for IP, (dist asc, ref asc) for L2.  Slots beyond nr hold id -1 and
- * -FLT_MAX / +FLT_MAX.
+ * by (score desc, ref asc) for IP, (dist asc, ref asc) for L2.  Slots beyond nr -- and the slots of
+ * scores that never enter faiss's heap: -inf (IP), +inf (L2), NaN -- hold id -1 and -FLT_MAX / +FLT_MAX.
  */
 void orc_knn(const float *q, int64_t nq, const float *r, int64_t nr, int64_t d, int metric, int64_t k,
              float *out_s, int64_t *out_j) {
@@ -504,6 +504,10 @@ void orc_knn(const float *q, int64_t nq, const float *r, int64_t nr, int64_t d, 
                 else l2_panel(q + i * d, rt, d, acc);
                 for (int jj = 0; jj < JB && j0 + jj < nr; ++jj) {
                     const float s = acc[jj];
+                    /* faiss fills the result heap with its neutral value (-FLT_MAX / +FLT_MAX, id -1) and a score
+                     * enters only if it beats the heap's top strictly: -inf (IP), +inf (L2) and NaN never do, and
+                     * their slots stay empty */
+                    if (!(keep_max ? (s > -FLT_MAX) : (s < FLT_MAX))) continue;
                     /* refs arrive in ascending order: a tie never displaces an earlier ref */
                     if (m == k) {
                         const int better = keep_max ? (s > bs[k - 1]) : (s < bs[k - 1]);

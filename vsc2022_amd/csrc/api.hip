@@ -54,9 +54,9 @@ int pack_half_any(const float* x, int64_t n, int dim, const HalfImage& h, int64_
 }
 
 int pack_into(const float* x, int64_t n, int dim, int mem, float* dst, int64_t rows_out, int dpad,
-                     Workspace& ws, hipStream_t stream, const HalfImage& h) {
+                     Workspace& ws, hipStream_t stream, const HalfImage& h, float kpad) {
     if (mem == VSC_MEM_DEVICE || n == 0) {
-        VSC_TRY(launch_pack_rows(x, n, dim, dst, rows_out, dpad, stream));
+        VSC_TRY(launch_pack_rows(x, n, dim, dst, rows_out, dpad, stream, kpad));
         if (h.rows) VSC_TRY(pack_half_any(x, n, dim, h, 0, h.rows_out, stream));
         return VSC_OK;
     }
@@ -67,7 +67,7 @@ int pack_into(const float* x, int64_t n, int dim, int mem, float* dst, int64_t r
         VSC_HIP(hipMemcpyAsync(ws.stage.p, x + r0 * dim, (size_t)rows * dim * 4, hipMemcpyHostToDevice, stream));
         const bool last = (r0 + rows == n);
         const int64_t out_rows = last ? rows_out - r0 : rows;
-        VSC_TRY(launch_pack_rows(ws.stage.as<float>(), rows, dim, dst + r0 * dpad, out_rows, dpad, stream));
+        VSC_TRY(launch_pack_rows(ws.stage.as<float>(), rows, dim, dst + r0 * dpad, out_rows, dpad, stream, kpad));
         if (h.rows) VSC_TRY(pack_half_any(ws.stage.as<float>(), rows, dim, h, r0, last ? h.rows_out - r0 : rows, stream));
         VSC_HIP(hipStreamSynchronize(stream));  // staging buffer is reused
     }
@@ -832,7 +832,8 @@ int pack_queries(vsc_index* idx, const float* q, int64_t nq, int q_mem, float** 
         h.rows = idx->ws.qh.as<_Float16>();
         h.norms = idx->ws.qn.as<float>();
     }
-    VSC_TRY(pack_into(q, nq, idx->dim, q_mem, idx->ws.qbuf.as<float>(), rows, idx->dpad, idx->ws, idx->stream, h));
+    // (queries are padded with -0.0 along k: the padded chain steps keep a -0.0 score, layout.hip pack_rows_kernel)
+    VSC_TRY(pack_into(q, nq, idx->dim, q_mem, idx->ws.qbuf.as<float>(), rows, idx->dpad, idx->ws, idx->stream, h, -0.0f));
     *out = idx->ws.qbuf.as<float>();
     return VSC_OK;
 }

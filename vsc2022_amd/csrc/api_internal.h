@@ -80,7 +80,7 @@ struct HalfImage {
 
 int pack_half_any(const float* x, int64_t n, int dim, const HalfImage& h, int64_t r0, int64_t rows_out, hipStream_t stream);
 int pack_into(const float* x, int64_t n, int dim, int mem, float* dst, int64_t rows_out, int dpad, Workspace& ws,
-              hipStream_t stream, const HalfImage& h = HalfImage());
+              hipStream_t stream, const HalfImage& h = HalfImage(), float kpad = 0.0f);
 
 }  // namespace vscmi
 

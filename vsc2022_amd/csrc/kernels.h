@@ -329,7 +329,7 @@ int pair_aggregate_device(const int32_t* hi, const int32_t* hj, const float* hs,
                           int32_t* out_q, int32_t* out_r, float* out_s, int64_t* out_first, int32_t* out_count, int64_t cap,
                           int64_t* n_pairs, hipStream_t);
 int launch_knn_to_hits(const int64_t* ids, int64_t nq, int k, int32_t* hi, int32_t* hj, hipStream_t);
-int launch_pack_rows(const float*, int64_t, int, float*, int64_t, int, hipStream_t);
+int launch_pack_rows(const float*, int64_t, int, float*, int64_t, int, hipStream_t, float kpad = 0.0f);
 int launch_row_normalize(const float*, int64_t, int, float*, hipStream_t);
 // dynamic LDS a tn_pair_kernel launch may ask for (working state + similarity tile): what launch_tn_pairs sets as the
 // kernel's limit and what tn_run_buckets plans its LDS-tile buckets against (a workgroup has 160 KiB on gfx950)

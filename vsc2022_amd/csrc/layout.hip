@@ -5,10 +5,13 @@
 
 namespace vscmi {
 
-// one thread per (row, group of 8 k): reads 8 floats, writes two float4
+// one thread per (row, group of 8 k): reads 8 floats, writes two float4.
+// `kpad` fills the coordinates dim..dpad-1.  Reference rows get +0.0, QUERY rows -0.0: the padded steps of the chain are then
+// fmaf(-0, +0, acc) = acc for every acc, -0.0 included (with +0 on both sides fmaf(+0, +0, -0.0) is +0.0, and a score that
+// underflowed to -0.0 came out as +0.0 whenever dim was no multiple of K_PAD).
 __global__ __launch_bounds__(256) void pack_rows_kernel(const float* __restrict__ src, int64_t n, int dim,
                                                         float* __restrict__ dst, int64_t rows_pad,
-                                                        int dpad) {
+                                                        int dpad, float kpad) {
     const int groups = dpad / 8;
     const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (x >= rows_pad * groups) return;
@@ -18,7 +21,7 @@ __global__ __launch_bounds__(256) void pack_rows_kernel(const float* __restrict_
 #pragma unroll
     for (int w = 0; w < 8; ++w) {
         const int k = g * 8 + w;
-        v[w] = (row < n && k < dim) ? src[row * dim + k] : 0.0f;
+        v[w] = k >= dim ? kpad : row < n ? src[row * dim + k] : 0.0f;
     }
     float4 even = make_float4(v[0], v[2], v[4], v[6]);
     float4 odd = make_float4(v[1], v[3], v[5], v[7]);
@@ -28,11 +31,11 @@ __global__ __launch_bounds__(256) void pack_rows_kernel(const float* __restrict_
 }
 
 int launch_pack_rows(const float* src, int64_t n, int dim, float* dst, int64_t rows_pad, int dpad,
-                     hipStream_t stream) {
+                     hipStream_t stream, float kpad) {
     const int64_t total = rows_pad * (dpad / 8);
     if (total <= 0) return VSC_OK;
     hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, src,
-                       n, dim, dst, rows_pad, dpad);
+                       n, dim, dst, rows_pad, dpad, kpad);
     VSC_HIP(hipGetLastError());
     return VSC_OK;
 }

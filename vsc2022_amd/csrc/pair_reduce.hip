@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256) void pa_score_keys_kernel(const float* __restr
                                                             uint32_t* __restrict__ rank) {
     const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (x >= n) return;
-    keys[x] = f2key(hs[x]);
+    keys[x] = f2key(hs[x] + 0.0f);   // (-0.0 == +0.0 in the stable score sort; the scores are read back through rank[])
     rank[x] = (uint32_t)x;
 }
 

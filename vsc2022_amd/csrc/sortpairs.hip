@@ -9,6 +9,7 @@
 //                    and first-appearance order IS the stable descending order of the pair scores.
 //
 // HBM-bound plumbing on <= 2K hits (12-16 B each) over the stable LSD radix sort of radix.h.
+#include <algorithm>
 #include <cfloat>
 #include <cstring>
 #include <utility>
@@ -18,23 +19,33 @@
 
 namespace vscmi {
 
+// Signed zeros: -0.0 and +0.0 are ONE score in the reference's comparisons (the stable sorts order them by row and ref), but
+// f2key separates them and the sorted key is also what the score is read back from.  With `tie_zeros` a zero is keyed as
+// +0.0 and its sign travels in bit 0 of the (row, ref) key, below the reference (row << 32 | ref << 1 | sign; rows and refs
+// are non-negative int32).  sort_hits_topk starts its passes at bit 1, so the sign is never sorted on, whatever bounds
+// the caller gives (the radix passes are whole 8-bit digits: a spare HIGH bit would be swept up by the last digit).
+// sort_hits_rowcol never compares scores: it keeps the plain keys.
 __global__ __launch_bounds__(256) void pack_hits_kernel(const int32_t* i, const int32_t* j,
                                                         const float* s, int64_t n, uint64_t* key64,
-                                                        uint32_t* key32) {
+                                                        uint32_t* key32, int tie_zeros) {
     const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (x >= n) return;
-    key64[x] = ((uint64_t)(uint32_t)i[x] << 32) | (uint32_t)j[x];
-    key32[x] = f2key(s[x]);
+    const float v = s[x];
+    const bool neg_zero = tie_zeros && v == 0.0f && (__float_as_uint(v) >> 31);
+    key64[x] = tie_zeros ? (((uint64_t)(uint32_t)i[x] << 32) | ((uint64_t)(uint32_t)j[x] << 1) | (uint64_t)neg_zero)
+                         : (((uint64_t)(uint32_t)i[x] << 32) | (uint32_t)j[x]);
+    key32[x] = f2key(neg_zero ? 0.0f : v);
 }
 
 __global__ __launch_bounds__(256) void unpack_hits_kernel(const uint64_t* key64, const uint32_t* key32,
                                                           int64_t n, int32_t* i, int32_t* j, float* s,
-                                                          int negate) {
+                                                          int negate, int tie_zeros) {
     const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (x >= n) return;
     i[x] = (int32_t)(key64[x] >> 32);
-    j[x] = (int32_t)(key64[x] & 0xffffffffu);
-    const float v = key2f(key32[x]);
+    const uint32_t low = (uint32_t)(key64[x] & 0xffffffffu);
+    j[x] = (int32_t)(tie_zeros ? low >> 1 : low);
+    const float v = (tie_zeros && (low & 1u)) ? -0.0f : key2f(key32[x]);
     s[x] = negate ? -v : v;
 }
 
@@ -61,20 +72,21 @@ int sort_hits_topk(ConstHitView h, int64_t n, int64_t K, int64_t max_i, int64_t 
     uint64_t* k64b = sc.w1.as<uint64_t>();
     uint32_t* k32a = sc.w2.as<uint32_t>();
     uint32_t* k32b = sc.w3.as<uint32_t>();
-    hipLaunchKernelGGL(pack_hits_kernel, dim3(grid_for(n)), dim3(256), 0, stream, h.i, h.j, h.s, n, k64a, k32a);
+    hipLaunchKernelGGL(pack_hits_kernel, dim3(grid_for(n)), dim3(256), 0, stream, h.i, h.j, h.s, n, k64a, k32a, 1);
     VSC_HIP(hipGetLastError());
     const int end_bit = 32 + bits_for((uint64_t)(max_i > 0 ? max_i : 1));
     VSC_TRY(sc.tmp.reserve(radix_tmp_bytes(n)));
     // (row, ref) ascending, then -- stably -- score descending
-    // (the reference rows occupy `max_j` bits of the low word: the passes over the zero bits above them are skipped)
-    int w = radix_sort_pairs<uint64_t, uint32_t>(k64a, k64b, k32a, k32b, n, 0, max_j > 0 ? bits_for((uint64_t)max_j) : 32, false,
+    // (the reference rows occupy `max_j` bits of the low word above the sign bit 0, which no pass looks at: the passes over
+    // the zero bits above them are skipped)
+    int w = radix_sort_pairs<uint64_t, uint32_t>(k64a, k64b, k32a, k32b, n, 1, 1 + (max_j > 0 ? bits_for((uint64_t)max_j) : 31), false,
                                                  sc.tmp.p, stream, 32, end_bit);
     if (w < 0) { set_error("radix sort launch failed"); return VSC_ERR_HIP; }
     if (w) { std::swap(k64a, k64b); std::swap(k32a, k32b); }  // sorted pairs now in (k64a, k32a)
     w = radix_sort_pairs<uint32_t, uint64_t>(k32a, k32b, k64a, k64b, n, 0, 32, true, sc.tmp.p, stream);
     if (w < 0) { set_error("radix sort launch failed"); return VSC_ERR_HIP; }
     if (w) { std::swap(k64a, k64b); std::swap(k32a, k32b); }
-    hipLaunchKernelGGL(unpack_hits_kernel, dim3(grid_for(m)), dim3(256), 0, stream, k64a, k32a, m, out.i, out.j, out.s, negate);
+    hipLaunchKernelGGL(unpack_hits_kernel, dim3(grid_for(m)), dim3(256), 0, stream, k64a, k32a, m, out.i, out.j, out.s, negate, 1);
     VSC_HIP(hipGetLastError());
     return VSC_OK;
 }
@@ -354,7 +366,11 @@ __global__ __launch_bounds__(256) void knn_keys_kernel(const int32_t* hi, const 
                                                        uint64_t* key64) {
     const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (x >= n) return;
-    key64[x] = ((uint64_t)(uint32_t)hi[x] << 32) | (uint32_t)~f2key(hs[x]);  // ascending = score descending
+    // (a zero is keyed as +0.0, its sign kept in bit 0, below the score key: row << 33 | ~key << 1 | sign, rows below 2^31;
+    // the sort starts at bit 1 -- see pack_hits_kernel)
+    const float v = hs[x];
+    const bool neg_zero = v == 0.0f && (__float_as_uint(v) >> 31);
+    key64[x] = ((uint64_t)(uint32_t)hi[x] << 33) | ((uint64_t)(uint32_t)~f2key(neg_zero ? 0.0f : v) << 1) | (uint64_t)neg_zero;  // ascending = score descending
 }
 
 __global__ __launch_bounds__(256) void knn_cut_kernel(const uint64_t* key64, const uint32_t* ref, int64_t n,
@@ -364,7 +380,7 @@ __global__ __launch_bounds__(256) void knn_cut_kernel(const uint64_t* key64, con
     const int64_t row = x / k;
     const int slot = (int)(x % k);
     // first element of the row: lower bound of (row << 32)
-    const uint64_t want = (uint64_t)row << 32;
+    const uint64_t want = (uint64_t)row << 33;
     int64_t lo = 0, hi = n;
     while (lo < hi) {
         const int64_t mid = (lo + hi) >> 1;
@@ -372,8 +388,8 @@ __global__ __launch_bounds__(256) void knn_cut_kernel(const uint64_t* key64, con
         else hi = mid;
     }
     const int64_t e = lo + slot;
-    const bool have = e < n && (int64_t)(key64[e] >> 32) == row;
-    out_s[x] = have ? key2f(~(uint32_t)(key64[e] & 0xffffffffu)) : -FLT_MAX;
+    const bool have = e < n && (int64_t)(key64[e] >> 33) == row;
+    out_s[x] = !have ? -FLT_MAX : (key64[e] & 1ull) ? -0.0f : key2f(~(uint32_t)((key64[e] >> 1) & 0xffffffffu));
     out_j[x] = have ? (int64_t)ref[e] : -1;
 }
 
@@ -393,14 +409,14 @@ int knn_from_hits(ConstHitView h, int64_t n, int64_t nq, int k, SortScratch& sc,
         VSC_HIP(hipGetLastError());
         // the sort ping-pongs between its buffers: work on a copy of the refs, the hit list stays intact
         VSC_HIP(hipMemcpyAsync(ra, h.j, (size_t)n * 4, hipMemcpyDeviceToDevice, stream));
-        const int end_bit = 32 + bits_for((uint64_t)(nq > 0 ? nq : 1));
+        const int end_bit = 33 + bits_for((uint64_t)(nq > 0 ? nq : 1));   // (bit 0: the sign of a zero, never sorted on)
         VSC_TRY(sc.tmp.reserve(radix_tmp_bytes(n)));
         // 1. refs ascending (payload: the row/score key) ...
         int w = radix_sort_pairs<uint32_t, uint64_t>(ra, rb, ka, kb, n, 0, 32, false, sc.tmp.p, stream);
         if (w < 0) { set_error("radix sort launch failed"); return VSC_ERR_HIP; }
         if (w) { std::swap(ka, kb); std::swap(ra, rb); }
         // 2. ... then, stably, row ascending / score descending
-        w = radix_sort_pairs<uint64_t, uint32_t>(ka, kb, ra, rb, n, 0, end_bit, false, sc.tmp.p, stream);
+        w = radix_sort_pairs<uint64_t, uint32_t>(ka, kb, ra, rb, n, 1, end_bit, false, sc.tmp.p, stream);
         if (w < 0) { set_error("radix sort launch failed"); return VSC_ERR_HIP; }
         if (w) { std::swap(ka, kb); std::swap(ra, rb); }
     }
@@ -465,13 +481,13 @@ int sort_hits_rowcol(ConstHitView h, int64_t n, SortScratch& sc, HitView out, in
     uint64_t* k64b = sc.w1.as<uint64_t>();
     uint32_t* k32a = sc.w2.as<uint32_t>();
     uint32_t* k32b = sc.w3.as<uint32_t>();
-    hipLaunchKernelGGL(pack_hits_kernel, dim3(grid_for(n)), dim3(256), 0, stream, h.i, h.j, h.s, n, k64a, k32a);
+    hipLaunchKernelGGL(pack_hits_kernel, dim3(grid_for(n)), dim3(256), 0, stream, h.i, h.j, h.s, n, k64a, k32a, 0);
     VSC_HIP(hipGetLastError());
     VSC_TRY(sc.tmp.reserve(radix_tmp_bytes(n)));
     const int w = radix_sort_pairs<uint64_t, uint32_t>(k64a, k64b, k32a, k32b, n, 0, 64, false, sc.tmp.p, stream);
     if (w < 0) { set_error("radix sort launch failed"); return VSC_ERR_HIP; }
     if (w) { std::swap(k64a, k64b); std::swap(k32a, k32b); }
-    hipLaunchKernelGGL(unpack_hits_kernel, dim3(grid_for(n)), dim3(256), 0, stream, k64a, k32a, n, out.i, out.j, out.s, negate);
+    hipLaunchKernelGGL(unpack_hits_kernel, dim3(grid_for(n)), dim3(256), 0, stream, k64a, k32a, n, out.i, out.j, out.s, negate, 0);
     VSC_HIP(hipGetLastError());
     return VSC_OK;
 }
