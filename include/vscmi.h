@@ -439,6 +439,62 @@ int vsc_tn_forward_sim(const float* sims, const int64_t* sims_off, const int32_t
 int vsc_tn_similarity(vsc_tn_ctx_t* ctx, int32_t q_vid, int32_t r_vid, float bias, float* out,
                       int64_t cap, int32_t* lq, int32_t* lr);
 
+/* ------------------------------------------------------------- DnS localisation on the device
+ * VCSLLocalizationDnS (vsc/baseline/dns_baseline.py:108-163) without a matrix leaving the GPU: the fine matrix of a pair
+ * (a torch model's output, or the region Chamfer similarity computed here) is blended with the coarse similarity inside
+ * the Temporal-Network kernel, aligned and scored.  Everything is opt-in: a context that never sees these calls behaves
+ * as before.
+ *
+ * Fine descriptors of a video are [L][R][D]: L the frame count of the same video in the context, 1 <= R <=
+ * VSC_FINE_MAX_REGIONS regions per frame, D = fdim values per region; VSC_FINE_ATT: fp32 values, VSC_FINE_BIN: bytes
+ * {0, 1} taken as 2 x - 1 in {-1, +1} (exact).  All inputs must be finite (documented, not checked).  The arithmetic,
+ * every step one correctly rounded fp32 operation (the library is built with -ffp-contract=off and no fast-math):
+ *   1. region matrix   G[i,a; j,b]: acc = +0; acc = fmaf(q[i,a,d], r[j,b,d], acc) for d ascending -- the engine's chain;
+ *                      BIN: followed by one division by (float)D
+ *   2. forward Chamfer A[i,j]: t = +0; for a = 0 .. R-1 in that order t = t + max_b G[i,a; j,b]; A = t / (float)R
+ *   3. backward        B[i,j]: the same with the roles of a and b swapped (sum over b ascending of max_a): the
+ *                      reference's model(ref, query).mT, from the same G
+ *   4. mapping         F0 = symmetric ? (A + B) / 2.0f : A;  F = F0 / 2.0f + 0.5f
+ *   5. blend           C = the coarse tile, vsc_tn_similarity's bits including + bias;
+ *                      S = geometric_mean ? sqrtf(fmaxf(F, 1e-7f) * fmaxf(C, 1e-7f)) : F   (the product rounded to fp32:
+ *                      numpy's np.sqrt(sim.clip(1e-7) * sim_cg.clip(1e-7)) on fp32 arrays)
+ *   6. alignment       S through the Temporal Network; box score max(S[q_lo:q_hi, r_lo:r_hi]) - bias as vsc_tn_localize
+ * The max of steps 2-3 is a plain fp32 maximum (G holds no -0.0: the chain starts from +0). */
+#define VSC_FINE_ATT 0
+#define VSC_FINE_BIN 1
+#define VSC_FINE_MAX_REGIONS 16
+/* Attach fine descriptors to a context: qfine / rfine = [total frames of that side][regions][fdim] in `mem` (host or
+ * device; host sources are staged in chunks), fp32 (ATT) or bytes (BIN); the frame counts and video offsets are the
+ * context's own.  Either pointer may be NULL: that side is left as it is -- unless regions, fdim or kind differ from
+ * what the context holds, which drops both sides first.  vsc_tn_set_queries drops the query side, whose frames it
+ * replaces.  The rows are kept as L R packed fp32 rows of fdim (padded to 64) in the engine's k-interleaved layout; BIN is
+ * stored as +-1 fp32 for now (a 1-bit store with an integer kernel is a follow-up).  VSC_ERR_INVALID for regions outside
+ * 1..VSC_FINE_MAX_REGIONS, fdim < 1 or an unknown kind. */
+int vsc_tn_set_fine(vsc_tn_ctx_t* ctx, const void* qfine, const void* rfine, int regions, int fdim, int kind, int mem);
+/* Bytes the context asked the device for to hold the fine descriptor rows of both sides (cf. vsc_tn_ref_bytes). */
+int64_t vsc_tn_fine_bytes(const vsc_tn_ctx_t* ctx);
+/* Stage 1: F (steps 1-4) of every pair of the list, row-major lq x lr, at out + out_off[p]; out_off[n_pairs] lies where
+ * `out` does (out_mem), cap is the capacity of `out` in floats.  VSC_ERR_CAPACITY with nothing written when a pair does
+ * not fit; VSC_ERR_INVALID when a side that has frames has no fine descriptors, or for a pair ordinal outside the
+ * context's videos (checked on the host copy of the list and again by the kernel, which skips the tile and raises an
+ * error word: nothing is read out of range).  One launch over (pair, tile) work items; stream and synchronisation as
+ * vsc_tn_localize. */
+int vsc_tn_fine_similarity(vsc_tn_ctx_t* ctx, const int32_t* pair_q, const int32_t* pair_r, int64_t n_pairs, int pairs_mem,
+                           int symmetric, float* out, const int64_t* out_off, int64_t cap, int out_mem);
+/* Stage 2: steps 5-6 for one localize_all batch.  `fine` is a slab of F matrices (stage 1's output or a torch model's),
+ * pair p row-major lq x lr at fine + fine_off[p]; fine and fine_off[n_pairs] lie in fine_mem.  A host slab is copied down
+ * once, up to the last cell a pair covers.  Without geometric_mean the fine matrices are aligned as they are and no
+ * descriptor is read.  Outputs, stream and synchronisation as vsc_tn_localize; the box table feeds vsc_tn_match_rows
+ * unchanged.  Both reference codecs: only the coarse side has one. */
+int vsc_tn_localize_fine(vsc_tn_ctx_t* ctx, const int32_t* pair_q, const int32_t* pair_r, int64_t n_pairs, int pairs_mem,
+                         const float* fine, const int64_t* fine_off, int fine_mem, int geometric_mean,
+                         const vsc_tn_params* params, float bias, int32_t* out_nbox, int32_t* out_boxes, float* out_boxmax,
+                         int out_mem);
+/* S (step 5) of one pair on the host: `fine` = its F matrix (lq x lr floats in fine_mem); out, cap, lq, lr as
+ * vsc_tn_similarity. */
+int vsc_tn_similarity_fine(vsc_tn_ctx_t* ctx, int32_t q_vid, int32_t r_vid, float bias, const float* fine, int fine_mem,
+                           int geometric_mean, float* out, int64_t cap, int32_t* lq, int32_t* lr);
+
 /* ------------------------------------------------------------- DTW / DP aligners
  * vcsl.vta.build_vta_model("DTW" / "DP") on the device (vsc2022_amd/vcsl/aligners.py spells both algorithms out choice
  * by choice; the boxes here are those of its host functions `dtw` / `dp` on the same fp32 matrices, integer for

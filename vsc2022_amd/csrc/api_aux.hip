@@ -580,6 +580,13 @@ struct vsc_tn_ctx {
     // [rows][2], the scan's scratch and control words, and the row columns when the caller wants them on the host
     DevBuf d_qts, d_rts, d_rowoff, d_tileoff, d_rowctl, d_rows[4];
     bool has_qts = false, has_rts = false;
+    // DnS fine descriptors (vsc_tn_set_fine): fine_regions packed fp32 rows of fine_dpad floats per frame of either side
+    // (bin: +-1), the scratch of vsc_tn_fine_similarity (work list, offsets, error word, dense output for host callers)
+    // and of vsc_tn_localize_fine / vsc_tn_similarity_fine (the fine slab of host callers, its offsets, frame counts)
+    int fine_regions = 0, fine_dim = 0, fine_dpad = 0, fine_kind = -1;
+    bool has_qfine = false, has_rfine = false;
+    int64_t qfine_bytes = 0, rfine_bytes = 0;
+    DevBuf qfine, rfine, d_fwork, d_foff, d_ferr, fine_out, fine_mat, d_flq, d_flr;
     Workspace ws;
     hipStream_t stream = nullptr;      // own_stream, or the caller's (vsc_tn_set_stream)
     hipStream_t own_stream = nullptr;
@@ -732,6 +739,8 @@ int vsc_tn_set_queries(vsc_tn_ctx_t* c, const float* qfeat, const int64_t* q_off
     }
     VSC_HIP(hipSetDevice(c->device));
     c->has_qts = false;  // (the table described the rows that are being replaced: vsc_tn_set_timestamps)
+    c->has_qfine = false;  // (... and so did the fine descriptors: vsc_tn_set_fine)
+    c->qfine_bytes = 0;
     // everything that can fail (allocation, packing, upload) runs on local state first: the context keeps its old,
     // consistent query side if any of it does, and takes the new offsets only once the device holds the new rows
     std::vector<int64_t> off(q_off, q_off + n_qvid + 1);
@@ -769,6 +778,8 @@ int vsc_tn_destroy(vsc_tn_ctx_t* c) {
     c->d_boxes.release(); c->d_bmax.release(); c->d_status.release(); c->slab.release(); c->sims.release();
     c->d_qts.release(); c->d_rts.release(); c->d_rowoff.release(); c->d_tileoff.release(); c->d_rowctl.release();
     for (auto& b : c->d_rows) b.release();
+    c->qfine.release(); c->rfine.release(); c->d_fwork.release(); c->d_foff.release(); c->d_ferr.release();
+    c->fine_out.release(); c->fine_mat.release(); c->d_flq.release(); c->d_flr.release();
     c->ws.release();
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
@@ -809,11 +820,14 @@ static int tn_pair_shapes(vsc_tn_ctx* c, const char* who, const int32_t* pair_q,
     return VSC_OK;
 }
 
-int vsc_tn_localize(vsc_tn_ctx_t* c, const int32_t* pair_q, const int32_t* pair_r, int64_t n_pairs,
-                    int pairs_mem, const vsc_tn_params* params, float bias, int32_t* out_nbox,
-                    int32_t* out_boxes, float* out_boxmax, int out_mem) {
+// vsc_tn_localize, and vsc_tn_localize_fine when `fine` is set: the slab of fine matrices (pair p at fine + fine_off[p],
+// both in fine_mem) is blended into the coarse tile (geometric) or aligned as it is.
+static int tn_localize_run(vsc_tn_ctx_t* c, const char* who, const int32_t* pair_q, const int32_t* pair_r, int64_t n_pairs,
+                           int pairs_mem, const float* fine, const int64_t* fine_off, int fine_mem, bool geometric,
+                           const vsc_tn_params* params, float bias, int32_t* out_nbox, int32_t* out_boxes, float* out_boxmax,
+                           int out_mem) {
     if (!c || n_pairs < 0 || !params || (n_pairs > 0 && (!pair_q || !pair_r || !out_nbox || !out_boxes || !out_boxmax))) {
-        set_error("vsc_tn_localize: invalid argument");
+        set_error("%s: invalid argument", who);
         return VSC_ERR_INVALID;
     }
     if (n_pairs == 0) return VSC_OK;
@@ -821,13 +835,32 @@ int vsc_tn_localize(vsc_tn_ctx_t* c, const int32_t* pair_q, const int32_t* pair_
         params->max_path < 0 || params->max_path >= VSC_TN_MAX_BOXES) {
         // max_path + 1 extractions can accept max_path + 1 boxes: more than the output holds would silently change
         // the IoU-suppression history
-        set_error("vsc_tn_localize: unsupported TN parameters (tn_top_k 1..16, tn_max_step 1..64, max_path 0..%d)",
+        set_error("%s: unsupported TN parameters (tn_top_k 1..16, tn_max_step 1..64, max_path 0..%d)", who,
                   VSC_TN_MAX_BOXES - 1);
         return VSC_ERR_INVALID;
     }
     VSC_HIP(hipSetDevice(c->device));
     std::vector<int32_t> lqs, lrs;
-    VSC_TRY(tn_pair_shapes(c, "vsc_tn_localize", pair_q, pair_r, n_pairs, pairs_mem, lqs, lrs));
+    VSC_TRY(tn_pair_shapes(c, who, pair_q, pair_r, n_pairs, pairs_mem, lqs, lrs));
+    const float* d_fine = fine;
+    const int64_t* d_foff = fine_off;
+    if (fine && fine_mem == VSC_MEM_HOST) {  // the part of the host slab the pairs cover goes down in one copy
+        int64_t extent = 0;
+        for (int64_t p = 0; p < n_pairs; ++p) {
+            const int64_t cells = (int64_t)lqs[(size_t)p] * lrs[(size_t)p];
+            if (fine_off[p] < 0) {
+                set_error("%s: pair %lld has a negative offset into the fine slab", who, (long long)p);
+                return VSC_ERR_INVALID;
+            }
+            if (cells) extent = std::max(extent, fine_off[p] + cells);
+        }
+        VSC_TRY(c->fine_mat.reserve((size_t)std::max<int64_t>(extent, 1) * 4));
+        VSC_TRY(c->d_foff.reserve((size_t)n_pairs * 8));
+        if (extent) VSC_HIP(hipMemcpyAsync(c->fine_mat.p, fine, (size_t)extent * 4, hipMemcpyHostToDevice, c->stream));
+        VSC_HIP(hipMemcpyAsync(c->d_foff.p, fine_off, (size_t)n_pairs * 8, hipMemcpyHostToDevice, c->stream));
+        d_fine = c->fine_mat.as<float>();
+        d_foff = c->d_foff.as<int64_t>();
+    }
     int32_t* d_nbox = out_nbox;
     int32_t* d_boxes = out_boxes;
     float* d_bmax = out_boxmax;
@@ -854,6 +887,21 @@ int vsc_tn_localize(vsc_tn_ctx_t* c, const int32_t* pair_q, const int32_t* pair_
     base.out_nbox = d_nbox;
     base.out_boxes = d_boxes;
     base.out_boxmax = d_bmax;
+    if (fine && geometric) {
+        base.fine = d_fine;
+        base.fine_off = d_foff;
+    } else if (fine) {
+        // the fine matrices are the aligner's input as they are: forward_sim mode on device memory (no descriptor is read)
+        VSC_TRY(c->d_flq.reserve((size_t)n_pairs * 4));
+        VSC_TRY(c->d_flr.reserve((size_t)n_pairs * 4));
+        VSC_HIP(hipMemcpyAsync(c->d_flq.p, lqs.data(), (size_t)n_pairs * 4, hipMemcpyHostToDevice, c->stream));
+        VSC_HIP(hipMemcpyAsync(c->d_flr.p, lrs.data(), (size_t)n_pairs * 4, hipMemcpyHostToDevice, c->stream));
+        base.rfeat_h = nullptr;
+        base.sims_in = d_fine;
+        base.sims_off = d_foff;
+        base.sims_lq = c->d_flq.as<int32_t>();
+        base.sims_lr = c->d_flr.as<int32_t>();
+    }
     VSC_TRY(tn_run_buckets(base, lqs, lrs, c->d_work, c->slab, c->stream));
     if (out_mem == VSC_MEM_HOST) {
         VSC_HIP(hipMemcpyAsync(out_nbox, d_nbox, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, c->stream));
@@ -862,6 +910,25 @@ int vsc_tn_localize(vsc_tn_ctx_t* c, const int32_t* pair_q, const int32_t* pair_
     }
     VSC_HIP(hipStreamSynchronize(c->stream));
     return VSC_OK;
+}
+
+int vsc_tn_localize(vsc_tn_ctx_t* c, const int32_t* pair_q, const int32_t* pair_r, int64_t n_pairs,
+                    int pairs_mem, const vsc_tn_params* params, float bias, int32_t* out_nbox,
+                    int32_t* out_boxes, float* out_boxmax, int out_mem) {
+    return tn_localize_run(c, "vsc_tn_localize", pair_q, pair_r, n_pairs, pairs_mem, nullptr, nullptr, VSC_MEM_HOST, false, params,
+                           bias, out_nbox, out_boxes, out_boxmax, out_mem);
+}
+
+int vsc_tn_localize_fine(vsc_tn_ctx_t* c, const int32_t* pair_q, const int32_t* pair_r, int64_t n_pairs, int pairs_mem,
+                         const float* fine, const int64_t* fine_off, int fine_mem, int geometric_mean,
+                         const vsc_tn_params* params, float bias, int32_t* out_nbox, int32_t* out_boxes, float* out_boxmax,
+                         int out_mem) {
+    if (n_pairs > 0 && (!fine || !fine_off)) {
+        set_error("vsc_tn_localize_fine: invalid argument (no fine slab)");
+        return VSC_ERR_INVALID;
+    }
+    return tn_localize_run(c, "vsc_tn_localize_fine", pair_q, pair_r, n_pairs, pairs_mem, fine, fine_off, fine_mem,
+                           geometric_mean != 0, params, bias, out_nbox, out_boxes, out_boxmax, out_mem);
 }
 
 int vsc_tn_forward_sim(const float* sims, const int64_t* sims_off, const int32_t* lq, const int32_t* lr,
@@ -1214,6 +1281,215 @@ int vsc_tn_similarity(vsc_tn_ctx_t* c, int32_t q_vid, int32_t r_vid, float bias,
                  c->dpad, bias, c->sims.as<float>(), c->rfeat_h.as<_Float16>()};
     VSC_TRY(launch_tn_sims(a, c->stream));
     VSC_HIP(hipMemcpyAsync(out, c->sims.p, (size_t)lq * lr * 4, hipMemcpyDeviceToHost, c->stream));
+    VSC_HIP(hipStreamSynchronize(c->stream));
+    return VSC_OK;
+}
+
+// ------------------------------------------------------------------------ DnS: fine descriptors, region Chamfer, blend
+
+// One side's fine descriptors -> `rows` packed fp32 rows at dst (rows_out written, those from `rows` on as zeros).  att:
+// fp32, packed like every other row upload; bin: {0, 1} bytes, converted to +-1 in bounded chunks first.
+static int tn_fine_store(vsc_tn_ctx* c, const void* x, int kind, int64_t rows, int mem, float* dst, int64_t rows_out) {
+    const int dim = c->fine_dim, dpad = c->fine_dpad;
+    if (kind == VSC_FINE_ATT) return pack_into(static_cast<const float*>(x), rows, dim, mem, dst, rows_out, dpad, c->ws, c->stream);
+    if (rows == 0) return launch_pack_rows(nullptr, 0, dim, dst, rows_out, dpad, c->stream);
+    Workspace& ws = c->ws;
+    const int64_t chunk_rows = std::max<int64_t>(1, (int64_t)(64ll << 20) / ((int64_t)dim * 4));
+    VSC_TRY(ws.dec.reserve((size_t)std::min(chunk_rows, rows) * dim * 4));
+    if (mem != VSC_MEM_DEVICE) VSC_TRY(ws.stage.reserve((size_t)std::min(chunk_rows, rows) * dim));
+    const uint8_t* bytes = static_cast<const uint8_t*>(x);
+    for (int64_t r0 = 0; r0 < rows; r0 += chunk_rows) {
+        const int64_t n = std::min(chunk_rows, rows - r0);
+        const uint8_t* src = bytes + r0 * dim;
+        if (mem != VSC_MEM_DEVICE) {
+            VSC_HIP(hipMemcpyAsync(ws.stage.p, src, (size_t)n * dim, hipMemcpyHostToDevice, c->stream));
+            src = ws.stage.as<uint8_t>();
+        }
+        VSC_TRY(launch_bin_to_pm1(src, n * dim, ws.dec.as<float>(), c->stream));
+        VSC_TRY(launch_pack_rows(ws.dec.as<float>(), n, dim, dst + r0 * dpad, r0 + n == rows ? rows_out - r0 : n, dpad, c->stream));
+        VSC_HIP(hipStreamSynchronize(c->stream));  // the buffers are reused
+    }
+    return VSC_OK;
+}
+
+int vsc_tn_set_fine(vsc_tn_ctx_t* c, const void* qfine, const void* rfine, int regions, int fdim, int kind, int mem) {
+    if (!c || regions < 1 || regions > VSC_FINE_MAX_REGIONS || fdim < 1 || (kind != VSC_FINE_ATT && kind != VSC_FINE_BIN)) {
+        set_error("vsc_tn_set_fine: invalid argument (regions 1..%d, fdim >= 1, kind VSC_FINE_ATT / VSC_FINE_BIN)", VSC_FINE_MAX_REGIONS);
+        return VSC_ERR_INVALID;
+    }
+    VSC_HIP(hipSetDevice(c->device));
+    if (regions != c->fine_regions || fdim != c->fine_dim || kind != c->fine_kind) {
+        // a side kept from another shape or kind could not meet the new one: both are dropped, the one given comes back below
+        c->has_qfine = c->has_rfine = false;
+        c->qfine_bytes = c->rfine_bytes = 0;
+    }
+    c->fine_regions = regions;
+    c->fine_dim = fdim;
+    c->fine_kind = kind;
+    c->fine_dpad = round_up(fdim, K_PAD);
+    struct Side { const void* x; int64_t frames; DevBuf* buf; bool* has; int64_t* bytes; };
+    Side sides[2] = {{qfine, c->q_off.back(), &c->qfine, &c->has_qfine, &c->qfine_bytes},
+                     {rfine, c->r_off.back(), &c->rfine, &c->has_rfine, &c->rfine_bytes}};
+    for (Side& s : sides) {
+        if (!s.x) continue;
+        *s.has = false;  // (until the new rows are down)
+        const int64_t rows = s.frames * regions;
+        // +64 rows of slack: the 64-row tiles of the last video's last frames read past its end (fine_sim.hip)
+        const int64_t rows_out = round_up64(rows + 64, ROW_PAD);
+        VSC_TRY(s.buf->reserve((size_t)rows_out * c->fine_dpad * 4));
+        VSC_TRY(tn_fine_store(c, s.x, kind, rows, mem, s.buf->as<float>(), rows_out));
+        *s.bytes = rows_out * c->fine_dpad * 4;
+        *s.has = true;
+    }
+    VSC_HIP(hipStreamSynchronize(c->stream));
+    return VSC_OK;
+}
+
+int64_t vsc_tn_fine_bytes(const vsc_tn_ctx_t* c) { return c ? c->qfine_bytes + c->rfine_bytes : 0; }
+
+int vsc_tn_fine_similarity(vsc_tn_ctx_t* c, const int32_t* pair_q, const int32_t* pair_r, int64_t n_pairs, int pairs_mem,
+                           int symmetric, float* out, const int64_t* out_off, int64_t cap, int out_mem) {
+    if (!c || n_pairs < 0 || cap < 0 || (n_pairs > 0 && (!pair_q || !pair_r || !out_off))) {
+        set_error("vsc_tn_fine_similarity: invalid argument");
+        return VSC_ERR_INVALID;
+    }
+    if (n_pairs == 0) return VSC_OK;
+    // (a side without frames needs no descriptors: no pair has a cell to fill)
+    if ((!c->has_qfine && c->q_off.back() > 0) || (!c->has_rfine && c->r_off.back() > 0)) {
+        set_error("vsc_tn_fine_similarity: the context has no %s fine descriptors (vsc_tn_set_fine)", c->has_qfine ? "reference" : "query");
+        return VSC_ERR_INVALID;
+    }
+    VSC_HIP(hipSetDevice(c->device));
+    std::vector<int32_t> lqs, lrs;
+    VSC_TRY(tn_pair_shapes(c, "vsc_tn_fine_similarity", pair_q, pair_r, n_pairs, pairs_mem, lqs, lrs));
+    std::vector<int64_t> off((size_t)n_pairs);
+    if (out_mem == VSC_MEM_HOST) memcpy(off.data(), out_off, (size_t)n_pairs * 8);
+    else {
+        VSC_HIP(hipMemcpyAsync(off.data(), out_off, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, c->stream));
+        VSC_HIP(hipStreamSynchronize(c->stream));
+    }
+    // capacity first: nothing is written when one pair does not fit
+    const int frames = fine_sim_frames(c->fine_regions);
+    int64_t total = 0, n_work = 0;
+    for (int64_t p = 0; p < n_pairs; ++p) {
+        const int64_t lq = lqs[(size_t)p], lr = lrs[(size_t)p], cells = lq * lr;
+        if (cells == 0) continue;
+        if (off[(size_t)p] < 0 || off[(size_t)p] + cells > cap || !out) {
+            set_error("vsc_tn_fine_similarity: pair %lld (%lld x %lld frames at offset %lld) does not fit the output capacity %lld",
+                      (long long)p, (long long)lq, (long long)lr, (long long)off[(size_t)p], (long long)cap);
+            return VSC_ERR_CAPACITY;
+        }
+        total += cells;
+        n_work += ((lq + frames - 1) / frames) * ((lr + frames - 1) / frames);
+    }
+    if (n_work == 0) return VSC_OK;
+    if (n_work > 0x7fffffffLL / 3) {
+        set_error("vsc_tn_fine_similarity: %lld tiles in one call are beyond the supported size", (long long)n_work);
+        return VSC_ERR_INVALID;
+    }
+    // the work list: (pair, tile), pair after pair -- long and short pairs share the launch
+    std::vector<int32_t> work;
+    work.reserve((size_t)n_work * 3);
+    std::vector<int64_t> dense;  // host callers: the device copy is dense, the matrices are scattered after the copy back
+    if (out_mem == VSC_MEM_HOST) dense.resize((size_t)n_pairs);
+    int64_t fill = 0;
+    for (int64_t p = 0; p < n_pairs; ++p) {
+        const int lq = lqs[(size_t)p], lr = lrs[(size_t)p];
+        if (out_mem == VSC_MEM_HOST) dense[(size_t)p] = fill;
+        fill += (int64_t)lq * lr;
+        if (lq == 0 || lr == 0) continue;
+        for (int qf = 0; qf < lq; qf += frames)
+            for (int rf = 0; rf < lr; rf += frames) {
+                work.push_back((int32_t)p);
+                work.push_back(qf);
+                work.push_back(rf);
+            }
+    }
+    VSC_TRY(c->d_fwork.reserve(work.size() * 4));
+    VSC_TRY(c->d_ferr.reserve(16));
+    VSC_HIP(hipMemcpyAsync(c->d_fwork.p, work.data(), work.size() * 4, hipMemcpyHostToDevice, c->stream));
+    VSC_HIP(hipMemsetAsync(c->d_ferr.p, 0, sizeof(int), c->stream));
+    FineSimArgs a;
+    memset(&a, 0, sizeof(a));
+    a.qfine = c->qfine.as<float>();
+    a.rfine = c->rfine.as<float>();
+    a.q_off = c->d_qoff.as<int64_t>();
+    a.r_off = c->d_roff.as<int64_t>();
+    a.n_qvid = c->n_qvid;
+    a.n_rvid = c->n_rvid;
+    a.pair_q = c->d_pq.as<int32_t>();
+    a.pair_r = c->d_pr.as<int32_t>();
+    a.work = c->d_fwork.as<int32_t>();
+    a.n_work = (int)n_work;
+    a.regions = c->fine_regions;
+    a.fdim = c->fine_dim;
+    a.dpad = c->fine_dpad;
+    a.bin = c->fine_kind == VSC_FINE_BIN;
+    a.symmetric = symmetric != 0;
+    a.err = c->d_ferr.as<int>();
+    if (out_mem == VSC_MEM_HOST) {
+        VSC_TRY(c->fine_out.reserve((size_t)total * 4));
+        VSC_TRY(c->d_foff.reserve((size_t)n_pairs * 8));
+        VSC_HIP(hipMemcpyAsync(c->d_foff.p, dense.data(), (size_t)n_pairs * 8, hipMemcpyHostToDevice, c->stream));
+        a.out = c->fine_out.as<float>();
+        a.out_off = c->d_foff.as<int64_t>();
+    } else {
+        a.out = out;
+        a.out_off = out_off;
+    }
+    VSC_TRY(launch_fine_sim(a, c->stream));
+    int err = 0;
+    VSC_HIP(hipMemcpyAsync(&err, c->d_ferr.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    std::vector<float> back;
+    if (out_mem == VSC_MEM_HOST) {
+        back.resize((size_t)total);
+        VSC_HIP(hipMemcpyAsync(back.data(), c->fine_out.p, (size_t)total * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    VSC_HIP(hipStreamSynchronize(c->stream));  // (the host work list is read by the copy above)
+    if (err) {
+        set_error("vsc_tn_fine_similarity: a pair has a video ordinal out of range (tiles skipped)");
+        return VSC_ERR_INVALID;
+    }
+    if (out_mem == VSC_MEM_HOST)
+        for (int64_t p = 0; p < n_pairs; ++p) {
+            const int64_t cells = (int64_t)lqs[(size_t)p] * lrs[(size_t)p];
+            if (cells) memcpy(out + off[(size_t)p], back.data() + dense[(size_t)p], (size_t)cells * 4);
+        }
+    return VSC_OK;
+}
+
+int vsc_tn_similarity_fine(vsc_tn_ctx_t* c, int32_t q_vid, int32_t r_vid, float bias, const float* fine, int fine_mem,
+                           int geometric_mean, float* out, int64_t cap, int32_t* lq_out, int32_t* lr_out) {
+    if (!c || q_vid < 0 || q_vid >= c->n_qvid || r_vid < 0 || r_vid >= c->n_rvid) {
+        set_error("vsc_tn_similarity_fine: invalid argument");
+        return VSC_ERR_INVALID;
+    }
+    const int64_t lq = c->q_off[q_vid + 1] - c->q_off[q_vid], lr = c->r_off[r_vid + 1] - c->r_off[r_vid];
+    if (lq_out) *lq_out = (int32_t)lq;
+    if (lr_out) *lr_out = (int32_t)lr;
+    if (lq * lr > cap || !out) {
+        set_error("vsc_tn_similarity_fine: output capacity %lld < %lld", (long long)cap, (long long)(lq * lr));
+        return VSC_ERR_CAPACITY;
+    }
+    if (lq * lr == 0) return VSC_OK;
+    if (!fine) {
+        set_error("vsc_tn_similarity_fine: invalid argument (no fine matrix)");
+        return VSC_ERR_INVALID;
+    }
+    VSC_HIP(hipSetDevice(c->device));
+    const size_t bytes = (size_t)lq * lr * 4;
+    if (!geometric_mean) {  // S = F
+        VSC_HIP(hipMemcpyAsync(out, fine, bytes, fine_mem == VSC_MEM_DEVICE ? hipMemcpyDeviceToHost : hipMemcpyHostToHost, c->stream));
+        VSC_HIP(hipStreamSynchronize(c->stream));
+        return VSC_OK;
+    }
+    const void* d_fine = nullptr;
+    VSC_TRY(to_device(fine, bytes, fine_mem, c->fine_mat, &d_fine, c->stream));
+    VSC_TRY(c->sims.reserve(bytes));
+    TnSimsArgs a{c->qfeat.as<float>(), c->rfeat.as<float>(), c->q_off[q_vid], c->r_off[r_vid], (int)lq, (int)lr,
+                 c->dpad, bias, c->sims.as<float>(), c->rfeat_h.as<_Float16>(), static_cast<const float*>(d_fine)};
+    VSC_TRY(launch_tn_sims(a, c->stream));
+    VSC_HIP(hipMemcpyAsync(out, c->sims.p, bytes, hipMemcpyDeviceToHost, c->stream));
     VSC_HIP(hipStreamSynchronize(c->stream));
     return VSC_OK;
 }

@@ -1,0 +1,138 @@
+// Region Chamfer similarity of a batch of candidate pairs (gfx950): the part of a ViSiL / DnS fine-grained student that
+// has no weights, F[i][j] of include/vscmi.h "DnS localisation on the device", steps 1-4.
+//
+// Replaces, per candidate pair (paths relative to /root/reference):
+//   vsc/baseline/dns_baseline.py:139-147   sim = model(query, ref); (sim + model(ref, query).mT) / 2; sim / 2 + 0.5
+// where `model` is the frame-to-frame Chamfer similarity on region descriptors [L, R, D]: inner products of all region
+// pairs, max over one side's regions, mean over the other's (vsc2022_amd.vsc.baseline.dns_baseline.ChamferSimilarity).
+//
+// Structure: the region matrix G of a pair ((Lq R) x (Lr R), 1.1 MB at 540 x 540 frames) never exists as a whole.  One
+// work item is FQ x FR WHOLE frames of one pair, FQ = FR = 64 / R (R = 9: 7 frames = 63 of 64 rows), so its 64 x 64 piece
+// of G holds every region pair of its frame pairs.  Four wavefronts compute one 32 x 32 block each with the block routine
+// of tn_sims.h (v_mfma_f32_32x32x2_f32, operands straight from L2 / HBM in the engine's k-interleaved layout, ascending-k
+// fp32 chain from +0: the bits of oracle.pair_sims on the region rows) and leave it in LDS; one lane per (frame pair,
+// region) takes the row and column maxima, one lane per frame pair sums them in region order and writes F.  The work
+// list is (pair, tile): long and short pairs share a launch.  No atomics on floats; every F is written exactly once.
+// Rows past a video's last frame read the (zero padded) neighbour rows: their products land in rows / columns of the LDS
+// piece that no maximum reads.  The k padding is zeros: fmaf(0, 0, acc) == acc.
+//
+// Bound: matrix cores.  2 Lq Lr R^2 D flops per pair against 4 D R (Lq + Lr) bytes of region rows read once from HBM and
+// 4 Lq Lr bytes written: 0.3 GFLOP against 2.2 MB at 60 x 60 frames, R = 9, D = 512 (135 flop / byte; the exact fp32
+// similarity kernel reaches 137 TFLOP/s).  Every tile re-reads its rows from L2 (no operand staging in LDS) and a
+// quarter of the lanes idle in the reductions at R = 16 -- UNMEASURED until profiles/dns_device.md holds a run of
+// scripts/bench_dns_device.py.
+#include "kernels.h"
+#include "tn_sims.h"
+
+namespace vscmi {
+
+constexpr int FS_TILE = 64;  // region rows / columns of one work item (2 x 2 MFMA blocks)
+constexpr int FS_LD = 65;    // leading dimension of the LDS piece (odd: the column walks of the backward maxima spread over banks)
+
+int fine_sim_frames(int regions) { return FS_TILE / regions; }
+
+__global__ __launch_bounds__(256) void fine_sim_kernel(FineSimArgs a) {
+    __shared__ float G[FS_TILE * FS_LD];
+    __shared__ float fwd[FS_TILE * FS_TILE];  // [frame pair][a]: max over b
+    __shared__ float bwd[FS_TILE * FS_TILE];  // [frame pair][b]: max over a (symmetric only)
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, hi = lane >> 5, l31 = lane & 31;
+    const int32_t* w = a.work + 3 * (int64_t)blockIdx.x;
+    const int p = w[0], qf0 = w[1], rf0 = w[2];
+    const int qv = a.pair_q[p], rv = a.pair_r[p];
+    if (qv < 0 || qv >= a.n_qvid || rv < 0 || rv >= a.n_rvid) {  // (uniform over the workgroup)
+        if (tid == 0) atomicOr(a.err, 1);
+        return;
+    }
+    const int64_t q0 = a.q_off[qv], r0 = a.r_off[rv];
+    const int lq = (int)(a.q_off[qv + 1] - q0), lr = (int)(a.r_off[rv + 1] - r0);
+    const int R = a.regions, F = FS_TILE / R;
+    if (qf0 < 0 || rf0 < 0 || qf0 >= lq || rf0 >= lr) return;  // (the host builds the list from the same offsets)
+    const int nfq = lq - qf0 < F ? lq - qf0 : F, nfr = lr - rf0 < F ? lr - rf0 : F;
+
+    // ---- 1. the 64 x 64 piece of G: one 32 x 32 block per wavefront, K ascending; blocks of padding only are skipped ----
+    const int qb = (wave >> 1) * 32, rb = (wave & 1) * 32;
+    if (qb < nfq * R && rb < nfr * R) {
+        const float* ap = a.qfine + ((q0 + qf0) * R + qb + l31) * a.dpad + hi * 4;
+        const float* bp = a.rfine + ((r0 + rf0) * R + rb + l31) * a.dpad + hi * 4;
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+        const int nkg = a.dpad / 8;
+#pragma unroll 4
+        for (int g = 0; g < nkg; ++g) {
+            const f32x4 av = *reinterpret_cast<const f32x4*>(ap + g * 8);
+            const f32x4 bv = *reinterpret_cast<const f32x4*>(bp + g * 8);
+#pragma unroll
+            for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], bv[s], acc, 0, 0, 0);
+        }
+        const float width = (float)a.fdim;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = qb + (r & 3) + 8 * (r >> 2) + 4 * hi;
+            G[row * FS_LD + rb + l31] = a.bin ? __fdiv_rn(acc[r], width) : acc[r];
+        }
+    }
+    __syncthreads();
+
+    // ---- 2. maxima: one lane per (frame pair, region) ----
+    const int nfp = nfq * nfr;
+    for (int x = tid; x < nfp * R; x += 256) {
+        const int fp = x / R, c = x - fp * R;
+        const int i = fp / nfr, j = fp - i * nfr;
+        const float* g = G + (i * R + c) * FS_LD + j * R;  // region c of query frame i against the regions of frame j
+        float m = g[0];
+        for (int b = 1; b < R; ++b) {
+            const float v = g[b];
+            m = v > m ? v : m;
+        }
+        fwd[x] = m;
+        if (a.symmetric) {
+            const float* h = G + (i * R) * FS_LD + j * R + c;  // region c of reference frame j against the regions of frame i
+            float m2 = h[0];
+            for (int b = 1; b < R; ++b) {
+                const float v = h[b * FS_LD];
+                m2 = v > m2 ? v : m2;
+            }
+            bwd[x] = m2;
+        }
+    }
+    __syncthreads();
+
+    // ---- 3. sums in region order, the mapping to [0, 1]: one lane per frame pair ----
+    const float regions = (float)R;
+    float* out = a.out + a.out_off[p];
+    for (int x = tid; x < nfp; x += 256) {
+        const int i = x / nfr, j = x - i * nfr;
+        float t = 0.0f;
+        for (int c = 0; c < R; ++c) t = __fadd_rn(t, fwd[x * R + c]);
+        float f0 = __fdiv_rn(t, regions);
+        if (a.symmetric) {
+            float u = 0.0f;
+            for (int c = 0; c < R; ++c) u = __fadd_rn(u, bwd[x * R + c]);
+            f0 = __fdiv_rn(__fadd_rn(f0, __fdiv_rn(u, regions)), 2.0f);
+        }
+        out[(int64_t)(qf0 + i) * lr + rf0 + j] = __fadd_rn(__fdiv_rn(f0, 2.0f), 0.5f);
+    }
+}
+
+int launch_fine_sim(const FineSimArgs& a, hipStream_t stream) {
+    if (a.n_work <= 0) return VSC_OK;
+    hipLaunchKernelGGL(fine_sim_kernel, dim3((unsigned)a.n_work), dim3(256), 0, stream, a);
+    VSC_HIP(hipGetLastError());
+    return VSC_OK;
+}
+
+// bin descriptors: {0, 1} bytes -> 2 x - 1 as fp32 (exact)
+__global__ __launch_bounds__(256) void bin_to_pm1_kernel(const uint8_t* __restrict__ src, int64_t n, float* __restrict__ dst) {
+    const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (x < n) dst[x] = 2.0f * (float)src[x] - 1.0f;
+}
+
+int launch_bin_to_pm1(const uint8_t* src, int64_t n, float* dst, hipStream_t stream) {
+    if (n <= 0) return VSC_OK;
+    hipLaunchKernelGGL(bin_to_pm1_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, src, n, dst);
+    VSC_HIP(hipGetLastError());
+    return VSC_OK;
+}
+
+}  // namespace vscmi

@@ -181,10 +181,24 @@ struct TnPairArgs {
     // SQfp16 context: the reference rows as half floats, [rows][dpad] in natural k order, instead of rfeat (nullptr:
     // rfeat, packed fp32).  The query side is packed fp32 either way
     const _Float16* rfeat_h;
+    // DnS blend (vsc_tn_localize_fine with geometric_mean; nullptr: none): the fine matrix F of pair p, row-major lq x lr at
+    // fine + fine_off[p]; the tile becomes sqrtf(fmaxf(F, 1e-7f) * fmaxf(tile, 1e-7f)) before anything reads it
+    const float* fine; const int64_t* fine_off;
 };
 struct TnSimsArgs {
     const float* qfeat; const float* rfeat; int64_t qrow0, rrow0; int lq, lr, dpad; float bias; float* out;
     const _Float16* rfeat_h;  // as in TnPairArgs
+    const float* fine;        // the pair's fine matrix (lq x lr) to blend with, as in TnPairArgs; nullptr: none
+};
+// Region Chamfer similarity of a batch of pairs (fine_sim.hip): one work item = FQ x FR whole frames of one pair
+struct FineSimArgs {
+    const float* qfine; const float* rfine;  // packed fp32 rows, regions rows per frame, dpad floats each
+    const int64_t* q_off; const int64_t* r_off; int64_t n_qvid, n_rvid;  // the context's frame offsets per video
+    const int32_t* pair_q; const int32_t* pair_r;
+    const int32_t* work; int n_work;  // [n_work][3]: pair, first query frame, first reference frame of the tile
+    int regions, fdim, dpad, bin, symmetric;
+    float* out; const int64_t* out_off;  // F of pair p, row-major lq x lr, at out + out_off[p]
+    int* err;  // error word: bit 0 = a pair ordinal outside the context's videos (that work item is skipped)
 };
 
 // DTW / DP aligners (align.hip): one candidate pair per single-wavefront workgroup, as tn_pair_kernel; the fields the
@@ -337,6 +351,9 @@ constexpr size_t TN_LAUNCH_LDS_MAX = 158 * 1024;
 size_t tn_state_bytes_host(int, int, int, int idx_bytes = 2);
 int launch_tn_pairs(const TnPairArgs&, size_t, hipStream_t);
 int launch_tn_sims(const TnSimsArgs&, hipStream_t);
+int fine_sim_frames(int regions);  // frames per side of a work item of launch_fine_sim
+int launch_fine_sim(const FineSimArgs&, hipStream_t);
+int launch_bin_to_pm1(const uint8_t*, int64_t, float*, hipStream_t);
 int launch_align_pairs(const AlignArgs&, size_t, hipStream_t);
 int64_t match_rows_tiles(int64_t n_pairs);
 int launch_match_rows_scan(const MatchRowsArgs&, hipStream_t);

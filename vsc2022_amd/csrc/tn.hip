@@ -121,7 +121,9 @@ __device__ unsigned long long tn_prof[8];
 #define TN_T(k) do {} while (0)
 #endif
 
-template <class IDX, bool GSTATE, bool RH16>
+// FINE: the DnS blend (vsc_tn_localize_fine with geometric_mean) -- the coarse tile is combined with the pair's fine
+// matrix before the aligner reads it; every other launch instantiates FINE = false and keeps its code
+template <class IDX, bool GSTATE, bool RH16, bool FINE = false>
 __global__ __launch_bounds__(64) void tn_pair_kernel(TnPairArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem_lds[];
     // working state: LDS, or this workgroup's slice of the HBM state slab (over-long videos; a single wavefront per
@@ -195,6 +197,17 @@ __global__ __launch_bounds__(64) void tn_pair_kernel(TnPairArgs a) {
     TN_T0();
     // ---- 1. similarity tile on the matrix cores: 32x32 output blocks, K ascending ----
     if (!a.sims_in) tn_sims_tile<RH16>(a, qrow0, rrow0, lq, lr, sims, lane);
+    if constexpr (FINE) {
+        // ---- 1b. blend: S = sqrt(max(F, 1e-7) * max(C, 1e-7)), one correctly rounded fp32 operation each (numpy's
+        // np.sqrt(sim.clip(1e-7) * coarse.clip(1e-7))); sqrtf is the correctly rounded square root (__fsqrt_rn is the
+        // hardware's approximate one in this toolchain).  The tile's elements were written by other lanes
+        __threadfence_block();
+        __syncthreads();
+        const float* fine = a.fine + a.fine_off[pidx];
+        const int64_t cells = (int64_t)lq * lr;
+        for (int64_t x = lane; x < cells; x += 64)
+            sims[x] = sqrtf(__fmul_rn(fmaxf(fine[x], 1e-7f), fmaxf(sims[x], 1e-7f)));
+    }
     for (int x = lane; x < zero_words; x += 64) zero[x] = 0;
     __threadfence_block();
     __syncthreads();
@@ -672,16 +685,16 @@ size_t tn_state_bytes_host(int max_lq, int top_cap, int ms, int idx_bytes) {
     return b;
 }
 
-template <bool RH16>
+template <bool RH16, bool FINE>
 static int launch_tn_pairs_from(const TnPairArgs& a, size_t lds_bytes, hipStream_t stream) {
     static PerDeviceOnce once;  // (one per reference source: the attribute belongs to the instantiation)
     if (a.state) {  // over-long videos: state in the HBM slab, 32-bit indices
-        hipLaunchKernelGGL((tn_pair_kernel<int, true, RH16>), dim3((unsigned)a.n_work), dim3(64), 0, stream, a);
+        hipLaunchKernelGGL((tn_pair_kernel<int, true, RH16, FINE>), dim3((unsigned)a.n_work), dim3(64), 0, stream, a);
         VSC_HIP(hipGetLastError());
         return VSC_OK;
     }
     if (once.first()) {
-        VSC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&tn_pair_kernel<short, false, RH16>),
+        VSC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&tn_pair_kernel<short, false, RH16, FINE>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)TN_LAUNCH_LDS_MAX));
         once.commit();
     }
@@ -689,7 +702,7 @@ static int launch_tn_pairs_from(const TnPairArgs& a, size_t lds_bytes, hipStream
         set_error("TN: a launch of %zu bytes of LDS is beyond the limit of %zu", lds_bytes, TN_LAUNCH_LDS_MAX);
         return VSC_ERR_INVALID;
     }
-    hipLaunchKernelGGL((tn_pair_kernel<short, false, RH16>), dim3((unsigned)a.n_work), dim3(64), lds_bytes, stream, a);
+    hipLaunchKernelGGL((tn_pair_kernel<short, false, RH16, FINE>), dim3((unsigned)a.n_work), dim3(64), lds_bytes, stream, a);
     VSC_HIP(hipGetLastError());
     return VSC_OK;
 }
@@ -697,12 +710,14 @@ static int launch_tn_pairs_from(const TnPairArgs& a, size_t lds_bytes, hipStream
 int launch_tn_pairs(const TnPairArgs& a, size_t lds_bytes, hipStream_t stream) {
     if (a.n_work <= 0) return VSC_OK;
     // (forward_sim mode reads no descriptors: rfeat_h is never set there)
-    return a.rfeat_h ? launch_tn_pairs_from<true>(a, lds_bytes, stream) : launch_tn_pairs_from<false>(a, lds_bytes, stream);
+    if (a.fine && !a.sims_in)
+        return a.rfeat_h ? launch_tn_pairs_from<true, true>(a, lds_bytes, stream) : launch_tn_pairs_from<false, true>(a, lds_bytes, stream);
+    return a.rfeat_h ? launch_tn_pairs_from<true, false>(a, lds_bytes, stream) : launch_tn_pairs_from<false, false>(a, lds_bytes, stream);
 }
 
 // LocalizationWithMetadata.similarity (vsc/baseline/localization.py:33-36,48-54) for one pair:
 // out[lq][lr] = q.feature @ r.feature.T + bias, one 32x32 block per wavefront.
-template <bool RH16>
+template <bool RH16, bool FINE = false>
 __global__ __launch_bounds__(64) void tn_sims_kernel(TnSimsArgs a) {
     const int lane = threadIdx.x, hi = lane >> 5, l31 = lane & 31;
     const int qb = blockIdx.y * 32, rb = blockIdx.x * 32;
@@ -723,15 +738,23 @@ __global__ __launch_bounds__(64) void tn_sims_kernel(TnSimsArgs a) {
     for (int r = 0; r < 16; ++r) {
         const int q = qb + (r & 3) + 8 * (r >> 2) + 4 * hi;
         const int rr = rb + l31;
-        if (q < a.lq && rr < a.lr) a.out[(int64_t)q * a.lr + rr] = acc[r] + a.bias;
+        if (q < a.lq && rr < a.lr) {
+            const int64_t x = (int64_t)q * a.lr + rr;
+            const float c = acc[r] + a.bias;
+            if constexpr (FINE) a.out[x] = sqrtf(__fmul_rn(fmaxf(a.fine[x], 1e-7f), fmaxf(c, 1e-7f)));  // the blend of tn_pair_kernel
+            else a.out[x] = c;
+        }
     }
 }
 
 int launch_tn_sims(const TnSimsArgs& a, hipStream_t stream) {
     if (a.lq <= 0 || a.lr <= 0) return VSC_OK;
     const dim3 grid((a.lr + 31) / 32, (a.lq + 31) / 32);
-    if (a.rfeat_h) hipLaunchKernelGGL(tn_sims_kernel<true>, grid, dim3(64), 0, stream, a);
-    else hipLaunchKernelGGL(tn_sims_kernel<false>, grid, dim3(64), 0, stream, a);
+    if (a.fine) {
+        if (a.rfeat_h) hipLaunchKernelGGL((tn_sims_kernel<true, true>), grid, dim3(64), 0, stream, a);
+        else hipLaunchKernelGGL((tn_sims_kernel<false, true>), grid, dim3(64), 0, stream, a);
+    } else if (a.rfeat_h) hipLaunchKernelGGL((tn_sims_kernel<true, false>), grid, dim3(64), 0, stream, a);
+    else hipLaunchKernelGGL((tn_sims_kernel<false, false>), grid, dim3(64), 0, stream, a);
     VSC_HIP(hipGetLastError());
     return VSC_OK;
 }

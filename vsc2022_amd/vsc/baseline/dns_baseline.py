@@ -16,8 +16,19 @@ network is whatever `torch.jit.load` / the caller supplies: any callable `sim_mo
 Because `similarity()` is overridden, `localize_all` takes the reference's route of
 `vsc2022_amd.vsc.baseline.localization.VCSLLocalization`: one matrix per pair (the coarse part computed on the
 GPU by libvscmi), alignment of all of them in one `vsc_tn_forward_sim` call, MaxSim score per box.
+
+`on_device=True` (opt-in; the default is the route above, unchanged) keeps every matrix in HBM.  Stage 1 produces the
+fine matrices F = sim / 2 + 0.5 of a batch in one device slab: an exact `ChamferSimilarity` instance -- the part of a
+fine-grained student that has no weights -- runs in libvscmi on fine descriptors that went down once
+(`vsc_tn_set_fine`, `vsc_tn_fine_similarity`: region Chamfer on the matrix cores); any other model runs as before, per
+pair, on `torch_device` (a GPU), with its descriptors uploaded once per unique video of the batch.  Stage 2
+(`vsc_tn_localize_fine`) blends the slab with the coarse similarity inside the Temporal-Network kernel, aligns and
+scores; nothing is copied to the host before the box table.  The arithmetic is written down in include/vscmi.h ("DnS
+localisation on the device"): with a torch model both routes see the same F bits and return equal matches; with
+`ChamferSimilarity` the device route has the bits of the CPU restatement in tests/dns_fine_ref.py.
 """
 import argparse
+import ctypes
 import logging
 import os
 from typing import Dict, List, Mapping, Sequence, Tuple, Union
@@ -25,6 +36,7 @@ from typing import Dict, List, Mapping, Sequence, Tuple, Union
 import numpy as np
 import torch
 
+from vsc2022_amd import _lib
 from vsc2022_amd.vsc import metrics as M
 from vsc2022_amd.vsc import storage
 from vsc2022_amd.vsc.baseline.dns_index import Accelerator
@@ -45,19 +57,189 @@ def _by_id(features: FineFeatures) -> Dict[object, VideoFeature]:
     return {v.video_id: v for v in features}
 
 
+class ChamferSimilarity(torch.nn.Module):
+    """The ViSiL / DnS frame-to-frame region Chamfer similarity, the part of a fine-grained student that has no weights:
+    inner products of all region pairs of two frames, max over the second argument's regions, mean over the first's.
+    `a` [La, R, D], `b` [Lb, R, D] -> [La, Lb].  `fg_type` as the reference reads it: "bin" descriptors arrive rescaled
+    to {-1, +1} and their inner product is divided by the width.  A model like any other on the host route; with
+    `VCSLLocalizationDnS(on_device=True)` an instance of exactly this class is computed by libvscmi (fine_sim.hip)."""
+
+    def __init__(self, fg_type: str = "att"):
+        super().__init__()
+        self.fg_type = fg_type
+        self.student_type = "fg"
+
+    def forward(self, a, b):
+        s = torch.einsum("ird,jsd->ijrs", a, b)
+        if "bin" in self.fg_type:
+            s = s / a.shape[-1]
+        return s.max(dim=3).values.mean(dim=2)
+
+
 class VCSLLocalizationDnS(VCSLLocalizationMaxSim):
     def __init__(self, model, queries_fine: FineFeatures, refs_fine: FineFeatures,
                  queries_coarse: List[VideoFeature], refs_coarse: List[VideoFeature], model_type, device,
-                 symmetric: bool = True, geometric_mean: bool = True, **kwargs):
+                 symmetric: bool = True, geometric_mean: bool = True, on_device: bool = False, **kwargs):
+        # the reference stores what it was given (a torch.device or the --accelerator string) and only ever hands it
+        # to Tensor.to(); "cuda" is the ROCm device under PyTorch-ROCm
+        torch_device = device if isinstance(device, torch.device) else torch.device(device)
+        self._chamfer = type(model) is ChamferSimilarity
+        if on_device:  # (checked before the descriptors go anywhere)
+            if model_type != "TN":
+                raise ValueError(f"on_device=True aligns with the Temporal Network kernel: model_type {model_type!r} is not \"TN\"")
+            if type(self).score is not VCSLLocalizationMaxSim.score or type(self).similarity is not VCSLLocalizationDnS.similarity:
+                raise ValueError("on_device=True needs the stock MaxSim score and similarity: an override cannot run in the kernel")
+            if not self._chamfer and torch_device.type != "cuda":
+                raise ValueError(f"on_device=True runs a torch similarity model on a GPU device, not on {torch_device}")
         super().__init__(queries_coarse, refs_coarse, model_type, **kwargs)
         self.queries_fine = _by_id(queries_fine)
         self.refs_fine = _by_id(refs_fine)
         self.sim_model = model
-        # the reference stores what it was given (a torch.device or the --accelerator string) and only ever hands it
-        # to Tensor.to(); "cuda" is the ROCm device under PyTorch-ROCm
-        self.torch_device = device if isinstance(device, torch.device) else torch.device(device)
+        self.torch_device = torch_device
         self.symmetric = symmetric
         self.geometric_mean = geometric_mean
+        self.on_device = bool(on_device)
+        self._bound_stream = None
+        if self.on_device:
+            self._q_len = np.array([len(v) for v in self._q_videos], dtype=np.int64)
+            self._r_len = np.array([len(v) for v in self._r_videos], dtype=np.int64)
+            if self._chamfer:
+                self._upload_fine()
+
+    # -- on_device=True ----------------------------------------------------------------------------
+    def _upload_fine(self):
+        """The fine descriptors of both sides, in the order of the context's videos, down once (vsc_tn_set_fine)."""
+        binary = "bin" in self.sim_model.fg_type
+        sides = []
+        for videos, table in ((self._q_videos, self.queries_fine), (self._r_videos, self.refs_fine)):
+            parts = []
+            for v in videos:
+                x = np.asarray(table[v.video_id].feature)
+                if x.ndim != 3 or len(x) != len(v):
+                    raise ValueError(f"video {v.video_id!r}: fine descriptors of shape {x.shape} for {len(v)} frames ([L, R, D] expected)")
+                parts.append(x)
+            sides.append(parts)
+        shapes = {p.shape[1:] for parts in sides for p in parts}
+        if len(shapes) > 1:
+            raise ValueError(f"fine descriptors differ in regions x width: {sorted(shapes)}")
+        if not shapes:
+            return
+        regions, width = shapes.pop()
+        rows = [np.ascontiguousarray(np.concatenate(parts, axis=0), dtype=np.uint8 if binary else np.float32) if parts else None
+                for parts in sides]
+        _lib.check(_lib.lib().vsc_tn_set_fine(
+            self._ctx, rows[0].ctypes.data if rows[0] is not None and rows[0].size else None,
+            rows[1].ctypes.data if rows[1] is not None and rows[1].size else None, int(regions), int(width),
+            _lib.FINE_BIN if binary else _lib.FINE_ATT, _lib.MEM_HOST))
+
+    @property
+    def fine_bytes(self) -> int:
+        """Bytes of HBM the context holds for the fine descriptor rows (`ChamferSimilarity` with on_device=True)."""
+        return int(_lib.lib().vsc_tn_fine_bytes(self._ctx))
+
+    def _slab_device(self) -> torch.device:
+        return torch.device("cuda", self.device)
+
+    def _bind_stream(self):
+        """The context's launches follow torch's on torch's current stream (as engine.bind_aux_stream does for the
+        entry points without a handle): the slab torch wrote is read without a device-wide synchronisation."""
+        tdev = self._slab_device()
+        if os.environ.get("VSC_TORCH_STREAM", "1") == "0":
+            torch.cuda.synchronize(tdev)
+            return
+        st = torch.cuda.current_stream(tdev).cuda_stream
+        if self._bound_stream != st:
+            _lib.check(_lib.lib().vsc_tn_set_stream(self._ctx, ctypes.c_void_p(st), 0))
+            self._bound_stream = st
+
+    @torch.no_grad()
+    def _model_fine(self, q: torch.Tensor, r: torch.Tensor) -> torch.Tensor:
+        """F of one pair by the torch model: the statements of `similarity`, on `torch_device`."""
+        sim = self.sim_model(q, r)
+        if self.symmetric:
+            sim = (sim + self.sim_model(r, q).mT) / 2.0
+        return sim / 2.0 + 0.5
+
+    def _fine_tensor(self, table, video_id, cache) -> torch.Tensor:
+        t = cache.get(video_id)
+        if t is None:
+            t = torch.from_numpy(np.asarray(table[video_id].feature)).to(self.torch_device).float()
+            t = cache[video_id] = self._rescale_binaries(t)
+        return t
+
+    def _fine_slab(self, candidates, pair_q: np.ndarray, pair_r: np.ndarray):
+        """Stage 1: (slab, offsets) in HBM -- F of pair k, row-major, at slab[offsets[k]:]."""
+        n = len(candidates)
+        lq, lr = self._q_len[pair_q], self._r_len[pair_r]
+        cells = lq * lr
+        off = np.zeros(n, dtype=np.int64)
+        np.cumsum(cells[:-1], out=off[1:])
+        total = int(cells.sum())
+        tdev = self._slab_device()
+        slab = torch.empty(max(total, 1), dtype=torch.float32, device=tdev)
+        d_off = torch.from_numpy(off).to(tdev)
+        if self._chamfer:
+            self._bind_stream()
+            _lib.check(_lib.lib().vsc_tn_fine_similarity(
+                self._ctx, pair_q.ctypes.data, pair_r.ctypes.data, n, _lib.MEM_HOST, int(bool(self.symmetric)),
+                slab.data_ptr(), d_off.data_ptr(), total, _lib.MEM_DEVICE))
+            return slab, d_off
+        q_cache, r_cache = {}, {}  # one upload per unique video of the batch
+        for k, c in enumerate(candidates):
+            if cells[k] == 0:
+                continue
+            f = self._model_fine(self._fine_tensor(self.queries_fine, c.query_id, q_cache),
+                                 self._fine_tensor(self.refs_fine, c.ref_id, r_cache))
+            slab[int(off[k]) : int(off[k] + cells[k])].view(int(lq[k]), int(lr[k])).copy_(f)
+        self._bind_stream()
+        return slab, d_off
+
+    def _device_boxes(self, candidates):
+        """Both stages of a batch: the box table on the host, as `_fused_boxes` returns it."""
+        n = len(candidates)
+        pair_q, pair_r = self._pair_ordinals(candidates)
+        slab, d_off = self._fine_slab(candidates, pair_q, pair_r)
+        n_boxes = np.zeros(n, dtype=np.int32)
+        boxes = np.zeros((n, _lib.TN_MAX_BOXES, 4), dtype=np.int32)
+        box_max = np.zeros((n, _lib.TN_MAX_BOXES), dtype=np.float32)
+        _lib.check(_lib.lib().vsc_tn_localize_fine(
+            self._ctx, pair_q.ctypes.data, pair_r.ctypes.data, n, _lib.MEM_HOST, slab.data_ptr(), d_off.data_ptr(),
+            _lib.MEM_DEVICE, int(bool(self.geometric_mean)), ctypes.byref(self.model.params), float(self.similarity_bias),
+            n_boxes.ctypes.data, boxes.ctypes.data, box_max.ctypes.data, _lib.MEM_HOST))
+        return pair_q, pair_r, n_boxes, boxes, box_max
+
+    def localize_all(self, candidates: List[CandidatePair]) -> List[Match]:
+        if not self.on_device:
+            return super().localize_all(candidates)
+        candidates = list(candidates)
+        if not candidates:
+            return []
+        _, _, n_boxes, boxes, box_max = self._device_boxes(candidates)
+        matches: List[Match] = []
+        for k, candidate in enumerate(candidates):
+            for b in range(int(n_boxes[k])):
+                match = self._to_match(candidate, [int(v) for v in boxes[k, b]])
+                matches.append(match._replace(score=self._fused_score(candidate, box_max[k, b])))
+        return matches
+
+    def localize_table(self, candidates: List[CandidatePair]):
+        if not self.on_device:
+            return super().localize_table(candidates)
+        candidates = candidates if hasattr(candidates, "columns") else list(candidates)
+        if len(candidates) == 0:
+            return M.MatchTable.empty()
+        pair_q, pair_r, n_boxes, boxes, box_max = self._device_boxes(candidates)
+        return self._device_rows(candidates, pair_q, pair_r, n_boxes, boxes, box_max)
+
+    def _device_similarity_fine(self, candidate: CandidatePair) -> np.ndarray:
+        """S of one pair: stage 1 for it alone, blended by libvscmi (vsc_tn_similarity_fine)."""
+        pair_q, pair_r = self._pair_ordinals([candidate])
+        slab, _ = self._fine_slab([candidate], pair_q, pair_r)
+        out = np.empty((int(self._q_len[pair_q[0]]), int(self._r_len[pair_r[0]])), dtype=np.float32)
+        _lib.check(_lib.lib().vsc_tn_similarity_fine(
+            self._ctx, int(pair_q[0]), int(pair_r[0]), float(self.similarity_bias), slab.data_ptr(), _lib.MEM_DEVICE,
+            int(bool(self.geometric_mean)), out.ctypes.data, out.size, None, None))
+        return out
 
     def _rescale_binaries(self, x):
         if "bin" in getattr(self.sim_model, "fg_type", ""):
@@ -66,6 +248,8 @@ class VCSLLocalizationDnS(VCSLLocalizationMaxSim):
 
     @torch.no_grad()
     def similarity(self, candidate: CandidatePair):
+        if self.on_device:
+            return self._device_similarity_fine(candidate)
         query = torch.from_numpy(np.asarray(self.queries_fine[candidate.query_id].feature)).to(self.torch_device).float()
         ref = torch.from_numpy(np.asarray(self.refs_fine[candidate.ref_id].feature)).to(self.torch_device).float()
         query, ref = self._rescale_binaries(query), self._rescale_binaries(ref)
@@ -91,11 +275,13 @@ def search(queries: List[VideoFeature], refs: List[VideoFeature], retrieve_per_q
 
 def localize_and_verify(model, queries_fine: FineFeatures, refs_fine: FineFeatures, queries_coarse: List[VideoFeature],
                         refs_coarse: List[VideoFeature], candidates: Sequence[CandidatePair],
-                        localize_per_query: float = 5.0, device="cpu") -> List[Match]:
-    """Reference :183-227: the best `localize_per_query * len(queries_fine)` candidates, batches of 512 pairs."""
+                        localize_per_query: float = 5.0, device="cpu", on_device: bool = False) -> List[Match]:
+    """Reference :183-227: the best `localize_per_query * len(queries_fine)` candidates, batches of 512 pairs.
+    on_device: `VCSLLocalizationDnS(on_device=True)`, every matrix stays in HBM."""
     todo = candidates[: int(len(queries_fine) * localize_per_query)]
     aligner = VCSLLocalizationDnS(model, queries_fine, refs_fine, queries_coarse, refs_coarse, model_type="TN",
-                                  tn_max_step=5, min_length=4, concurrency=16, similarity_bias=0.5, device=device)
+                                  tn_max_step=5, min_length=4, concurrency=16, similarity_bias=0.5, device=device,
+                                  on_device=on_device)
     found: List[Match] = []
     batch = 512
     for start in range(0, len(todo), batch):
@@ -105,13 +291,14 @@ def localize_and_verify(model, queries_fine: FineFeatures, refs_fine: FineFeatur
 
 
 def match(model, queries_fine: FineFeatures, refs_fine: FineFeatures, queries_coarse: List[VideoFeature],
-          refs_coarse: List[VideoFeature], output_path: str, device) -> Tuple[str, str]:
+          refs_coarse: List[VideoFeature], output_path: str, device, on_device: bool = False) -> Tuple[str, str]:
     """Reference :230-258; returns the paths of candidates.csv and matches.csv."""
     pairs = search(queries_coarse, refs_coarse)
     os.makedirs(output_path, exist_ok=True)
     candidate_file = os.path.join(output_path, "candidates.csv")
     CandidatePair.write_csv(pairs, candidate_file)
-    found = localize_and_verify(model, queries_fine, refs_fine, queries_coarse, refs_coarse, pairs, device=device)
+    found = localize_and_verify(model, queries_fine, refs_fine, queries_coarse, refs_coarse, pairs, device=device,
+                                on_device=on_device)
     matches_file = os.path.join(output_path, "matches.csv")
     Match.write_csv(found, matches_file)
     return candidate_file, matches_file
@@ -130,6 +317,8 @@ def build_parser() -> argparse.ArgumentParser:
                    choices=[x.name.lower() for x in Accelerator], default="cpu", type=str)
     p.add_argument("--ground_truth", help="Path to the ground truth (labels) CSV file.", type=str)
     p.add_argument("--overwrite", help="Overwrite prediction files, if found.", action="store_true")
+    p.add_argument("--on_device", help="Keep the similarity matrices of the localisation in HBM (needs a GPU accelerator).",
+                   action="store_true")
     return p
 
 
@@ -149,7 +338,7 @@ def main(args):
     queries_coarse = storage.load_features(args.query_coarse_features, M.Dataset.QUERIES)
     refs_coarse = storage.load_features(args.ref_coarse_features, M.Dataset.REFS)
     candidate_file, match_file = match(model, queries_fine, refs_fine, queries_coarse, refs_coarse, args.output_path,
-                                       device)
+                                       device, on_device=args.on_device)
     if args.ground_truth:
         from vsc2022_amd.vsc.baseline.sscd_baseline import _report
 
