@@ -1,7 +1,7 @@
 // C ABI of libvscmi.so (declared in include/vscmi.h), part 1: errors, handles, options, streams, the images of the
 // reference rows (add / int8 upkeep), query packing, hit buffers, profile counters.  Host orchestration only: every
 // arithmetic step runs in the HIP kernels of the sibling translation units.  The searches live in api_search.hip and
-// api_knn.hip, the handle-less entry points and the Temporal Network in api_aux.hip.
+// api_knn.hip, the handle-less entry points in api_aux.hip and the Temporal Network in api_tn.hip.
 #include "api_internal.h"
 
 namespace vscmi {
@@ -367,15 +367,6 @@ int vsc_index_destroy(vsc_index_t* idx) {
     // collected --: its handle is never touched again; the device is drained instead
     if (idx->stream == idx->own_stream) (void)hipStreamSynchronize(idx->own_stream);
     else (void)hipDeviceSynchronize();
-    idx->ref.release();
-    idx->refh.release();
-    idx->refn.release();
-    idx->ref8.release();
-    idx->ref8m.release();
-    idx->i8_mu.release();
-    for (auto& b : idx->cand) b.release();
-    idx->cand_ids.release();
-    idx->ws.release();
     for (auto& e : idx->ev_pool) {
         (void)hipEventDestroy(e.first);
         (void)hipEventDestroy(e.second);
@@ -719,16 +710,11 @@ static int index_add(vsc_index_t* idx, const void* x, bool src16, int64_t n, int
             }
             VSC_HIP(hipStreamSynchronize(idx->stream));
         }
-        idx->ref.release();
-        idx->refh.release();
-        idx->refn.release();
-        idx->ref8.release();
-        idx->ref8m.release();
-        idx->ref = nb;
-        idx->refh = nh;
-        idx->refn = nn;
-        idx->ref8 = n8;
-        idx->ref8m = n8m;
+        idx->ref = std::move(nb);  // (the old rows are freed by the assignment)
+        idx->refh = std::move(nh);
+        idx->refn = std::move(nn);
+        idx->ref8 = std::move(n8);
+        idx->ref8m = std::move(n8m);
         idx->cap_rows = cap;
     }
     if (sq16(idx)) {

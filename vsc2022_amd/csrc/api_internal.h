@@ -1,6 +1,7 @@
 // Internal declarations shared by the translation units of the C ABI (api.hip: handles, options, index upkeep;
-// api_search.hip: the thresholded searches; api_knn.hip: k-NN; api_aux.hip: pair-max, row normalisation, Temporal
-// Network, aligners, match rows).  Nothing here is exported: include/vscmi.h is the ABI.
+// api_search.hip: the thresholded searches; api_knn.hip: k-NN; api_aux.hip: the device ops that own no handle -- pair-max,
+// pair aggregation, row normalisation, segment AP; api_tn.hip: the Temporal-Network contexts, the aligners, match rows, DnS
+// fine descriptors).  Nothing here is exported: include/vscmi.h is the ABI.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -48,22 +49,6 @@ struct Workspace {
     HitView hits_a() const { return {hA[0].as<int32_t>(), hA[1].as<int32_t>(), hA[2].as<float>()}; }
     HitView hits_b() const { return {hB[0].as<int32_t>(), hB[1].as<int32_t>(), hB[2].as<float>()}; }
     HitView hits_out() const { return {out[0].as<int32_t>(), out[1].as<int32_t>(), out[2].as<float>()}; }
-    void release() {
-        stage.release(); qbuf.release(); sample.release();
-        dec.release(); flag.release(); kparts.release(); kpartj.release();
-        for (auto& b : sk) b.release();
-        for (auto& b : tk) b.release();
-        qh.release(); qn.release(); ci.release(); cj.release(); segcnt.release(); rowthr.release(); slices.release();
-        q8.release(); pstat.release(); rt8.release(); rt8b.release(); rt8c.release(); rt8d.release(); tailfill.release();
-        for (auto& b : cs) b.release();
-        cstmp.release(); csn.release();
-        for (auto& b : dd) b.release();
-        for (auto& b : hA) b.release();
-        for (auto& b : hB) b.release();
-        ctl.release(); sort.release(); agg.release(); cnt.release();
-        for (auto& b : out) b.release();
-        parts.release(); partj.release(); mat.release(); maps0.release(); maps1.release();
-    }
 };
 
 // Bring raw fp32 rows (host or device) into the packed engine layout at dst (rows_out rows are
@@ -81,6 +66,20 @@ struct HalfImage {
 int pack_half_any(const float* x, int64_t n, int dim, const HalfImage& h, int64_t r0, int64_t rows_out, hipStream_t stream);
 int pack_into(const float* x, int64_t n, int dim, int mem, float* dst, int64_t rows_out, int dpad, Workspace& ws,
               hipStream_t stream, const HalfImage& h = HalfImage(), float kpad = 0.0f);
+
+// The state of the entry points that own no handle, one per device for the life of the process (api_aux.hip; also behind
+// vsc_tn_forward_sim / vsc_align_forward_sim in api_tn.hip).  A call holds `mu` from its first use of the context on.
+struct DeviceCtx {
+    hipStream_t stream = nullptr;      // own_stream, or the caller's (vsc_set_aux_stream)
+    hipStream_t own_stream = nullptr;
+    Workspace ws;
+    MetricScratch metric;  // vsc_match_metric
+    DevBuf metric_in[6];   // ... and its host-memory tables
+    std::mutex mu;
+};
+DeviceCtx* device_ctx(int device);  // nullptr: its stream could not be created
+// fetch `bytes` of a caller array into device memory (no copy if already there)
+int to_device(const void* p, size_t bytes, int mem, DevBuf& buf, const void** out, hipStream_t s);
 
 }  // namespace vscmi
 

@@ -9,13 +9,11 @@ namespace vscmi {
 // Scratch of the radix sorts (sortpairs.hip): two key and two value ping-pong buffers + the sort's own temporary.
 struct SortScratch {
     DevBuf w0, w1, w2, w3, tmp;
-    void release() { w0.release(); w1.release(); w2.release(); w3.release(); tmp.release(); }
 };
 // Scratch of the pair aggregation beyond the sorts' (pair_reduce.hip): the per-pair results, the final sort's ping-pong
 // buffers and the control words.
 struct PairAggScratch {
     DevBuf k2, v2a, v2b, rs, rfirst, rcnt, ctl;
-    void release() { k2.release(); v2a.release(); v2b.release(); rs.release(); rfirst.release(); rcnt.release(); ctl.release(); }
 };
 // A hit list on the device: (row, ref, score) in three parallel arrays.
 struct HitView { int32_t* i; int32_t* j; float* s; };

@@ -94,10 +94,26 @@ struct PerDeviceOnce {
     }
 };
 
-// growable device buffer
+// growable device buffer; owns its memory: freed with the object that holds it (after that object's stream has been
+// drained -- the destroy functions of the handles), moved but never copied
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    ~DevBuf() { release(); }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            release();
+            p = o.p;
+            bytes = o.bytes;
+            o.p = nullptr;
+            o.bytes = 0;
+        }
+        return *this;
+    }
     int reserve(size_t need) {
         if (need <= bytes) return VSC_OK;
         if (p) {

@@ -282,24 +282,13 @@ class _HostAligner:
         import ctypes
 
         from vsc2022_amd import _lib
-        from vsc2022_amd.vcsl.vta import unpack_boxes
+        from vsc2022_amd.vcsl.vta import pack_sims, unpack_boxes
 
         names = [name for name, _ in data]
-        mats = [_lib.f32c(sim) for _, sim in data]
-        n = len(mats)
+        n = len(names)
         if n == 0:
             return []
-        for m in mats:
-            if m.ndim != 2:
-                raise ValueError("forward_sim expects 2-D similarity matrices")
-        lq = np.array([m.shape[0] for m in mats], dtype=np.int32)
-        lr = np.array([m.shape[1] for m in mats], dtype=np.int32)
-        off = np.zeros(n + 1, dtype=np.int64)
-        np.cumsum(lq.astype(np.int64) * lr, out=off[1:])
-        flat = np.concatenate([m.reshape(-1) for m in mats]) if off[-1] else np.zeros(1, np.float32)
-        nbox = np.zeros(n, dtype=np.int32)
-        boxes = np.zeros((n, _lib.TN_MAX_BOXES, 4), dtype=np.int32)
-        bmax = np.zeros((n, _lib.TN_MAX_BOXES), dtype=np.float32)
+        mats, flat, off, lq, lr, nbox, boxes, bmax = pack_sims([sim for _, sim in data])
         status = np.zeros(n, dtype=np.int32)
         device = _lib.default_device() if self.device is None else self.device
         _lib.check(_lib.lib().vsc_align_forward_sim(

@@ -33,6 +33,26 @@ def unpack_boxes(nbox: np.ndarray, boxes: np.ndarray) -> List[List[List[int]]]:
     return [[[int(v) for v in boxes[p, b]] for b in range(int(nbox[p]))] for p in range(len(nbox))]
 
 
+def pack_sims(sims: Sequence[np.ndarray]):
+    """The arrays of a `vsc_tn_forward_sim` / `vsc_align_forward_sim` call over the (at least one) matrices `sims`:
+    `(mats, flat, off, lq, lr, nbox, boxes, bmax)` -- the matrices as float32, back to back in `flat` with pair p at
+    `off[p]`, their shapes, and the zeroed box table the call fills."""
+    mats = [_lib.f32c(sim) for sim in sims]
+    n = len(mats)
+    for m in mats:
+        if m.ndim != 2:
+            raise ValueError("forward_sim expects 2-D similarity matrices")
+    lq = np.array([m.shape[0] for m in mats], dtype=np.int32)
+    lr = np.array([m.shape[1] for m in mats], dtype=np.int32)
+    off = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(lq.astype(np.int64) * lr, out=off[1:])
+    flat = np.concatenate([m.reshape(-1) for m in mats]) if off[-1] else np.zeros(1, np.float32)
+    nbox = np.zeros(n, dtype=np.int32)
+    boxes = np.zeros((n, _lib.TN_MAX_BOXES, 4), dtype=np.int32)
+    bmax = np.zeros((n, _lib.TN_MAX_BOXES), dtype=np.float32)
+    return mats, flat, off, lq, lr, nbox, boxes, bmax
+
+
 class TN:
     """Temporal Network aligner.  `concurrency` (a multiprocessing pool size in VCSL) is accepted
     and ignored: every pair of a call is aligned concurrently on the GPU."""
@@ -44,24 +64,12 @@ class TN:
 
     def forward_sim(self, data: Sequence[Tuple[str, np.ndarray]]) -> List[Tuple[str, List[List[int]]]]:
         names = [name for name, _ in data]
-        mats = [_lib.f32c(sim) for _, sim in data]
-        n = len(mats)
-        if n == 0:
+        if not names:
             return []
-        for m in mats:
-            if m.ndim != 2:
-                raise ValueError("forward_sim expects 2-D similarity matrices")
-        lq = np.array([m.shape[0] for m in mats], dtype=np.int32)
-        lr = np.array([m.shape[1] for m in mats], dtype=np.int32)
-        off = np.zeros(n + 1, dtype=np.int64)
-        np.cumsum(lq.astype(np.int64) * lr, out=off[1:])
-        flat = np.concatenate([m.reshape(-1) for m in mats]) if off[-1] else np.zeros(1, np.float32)
-        nbox = np.zeros(n, dtype=np.int32)
-        boxes = np.zeros((n, _lib.TN_MAX_BOXES, 4), dtype=np.int32)
-        bmax = np.zeros((n, _lib.TN_MAX_BOXES), dtype=np.float32)
+        _, flat, off, lq, lr, nbox, boxes, bmax = pack_sims([sim for _, sim in data])
         device = _lib.default_device() if self.device is None else self.device
         _lib.check(_lib.lib().vsc_tn_forward_sim(
-            flat.ctypes.data, off.ctypes.data, lq.ctypes.data, lr.ctypes.data, n,
+            flat.ctypes.data, off.ctypes.data, lq.ctypes.data, lr.ctypes.data, len(names),
             ctypes.byref(self.params), nbox.ctypes.data, boxes.ctypes.data, bmax.ctypes.data, device))
         return list(zip(names, unpack_boxes(nbox, boxes)))
 
