@@ -459,26 +459,49 @@ int vsc_tn_similarity(vsc_tn_ctx_t* ctx, int32_t q_vid, int32_t r_vid, float bia
  *                      S = geometric_mean ? sqrtf(fmaxf(F, 1e-7f) * fmaxf(C, 1e-7f)) : F   (the product rounded to fp32:
  *                      numpy's np.sqrt(sim.clip(1e-7) * sim_cg.clip(1e-7)) on fp32 arrays)
  *   6. alignment       S through the Temporal Network; box score max(S[q_lo:q_hi, r_lo:r_hi]) - bias as vsc_tn_localize
- * The max of steps 2-3 is a plain fp32 maximum (G holds no -0.0: the chain starts from +0). */
+ * The max of steps 2-3 is a plain fp32 maximum (G holds no -0.0: the chain starts from +0).
+ *
+ * The 1-bit store (VSC_FINE_BITS, vsc_tn_set_fine_bits) keeps BIN descriptors as the bits they are and computes the same
+ * step 1 from integers.  With q, r in {-1, +1} every partial sum of the chain is an integer of magnitude <= D, so for
+ * D <= 2^24 no step rounds and, with the values read as bits (+1 = 1, -1 = 0),
+ *     acc == (float)(D - 2 popcount(q xor r))
+ * exactly; the same single division by (float)D follows.  Steps 2-6 are the same code.  Results are the BITS of the
+ * VSC_FINE_BIN store on the same descriptors, at 1/32 of its memory.
+ *   layout   one row per (frame, region) of ceil(D / 128) 16-byte words; bit d of the row = element d, i.e. bit d % 8 of
+ *            byte d / 8 -- numpy's np.packbits(x, axis=-1, bitorder="little").  The bits from D up to the end of the row
+ *            are zero on BOTH sides: they xor to zero and never enter a popcount (D in the formula is the true fdim).
+ *            64 zero rows of slack follow a side's last frame, as in the fp32 store.
+ *   masking  packed input carries ceil(D / 8) bytes per row; the unused high bits of a row's last byte are the caller's:
+ *            the library masks them, whatever they hold changes no result. */
 #define VSC_FINE_ATT 0
 #define VSC_FINE_BIN 1
+#define VSC_FINE_BITS 2 /* a context state only (vsc_tn_set_fine_bits): vsc_tn_set_fine refuses it as an unknown kind */
 #define VSC_FINE_MAX_REGIONS 16
 /* Attach fine descriptors to a context: qfine / rfine = [total frames of that side][regions][fdim] in `mem` (host or
  * device; host sources are staged in chunks), fp32 (ATT) or bytes (BIN); the frame counts and video offsets are the
  * context's own.  Either pointer may be NULL: that side is left as it is -- unless regions, fdim or kind differ from
  * what the context holds, which drops both sides first.  vsc_tn_set_queries drops the query side, whose frames it
  * replaces.  The rows are kept as L R packed fp32 rows of fdim (padded to 64) in the engine's k-interleaved layout; BIN is
- * stored as +-1 fp32 for now (a 1-bit store with an integer kernel is a follow-up).  VSC_ERR_INVALID for regions outside
+ * stored as +-1 fp32 here and as bits by vsc_tn_set_fine_bits.  VSC_ERR_INVALID for regions outside
  * 1..VSC_FINE_MAX_REGIONS, fdim < 1 or an unknown kind. */
 int vsc_tn_set_fine(vsc_tn_ctx_t* ctx, const void* qfine, const void* rfine, int regions, int fdim, int kind, int mem);
-/* Bytes the context asked the device for to hold the fine descriptor rows of both sides (cf. vsc_tn_ref_bytes). */
+/* Attach BIN descriptors to a context as bits (the VSC_FINE_BITS store above).  packed = 0: the input of VSC_FINE_BIN,
+ * bytes {0, 1}, [frames][regions][fdim]; packed = 1: already packed, [frames][regions][ceil(fdim / 8)] bytes as
+ * np.packbits(x, axis=-1, bitorder="little") makes them (tail bits masked here).  `mem`, a NULL side, changed regions /
+ * fdim, and vsc_tn_set_queries as for vsc_tn_set_fine; going from an ATT / BIN store to this one or back drops both
+ * sides first.  vsc_tn_fine_similarity then runs the popcount kernel; every other call is unchanged.  VSC_ERR_INVALID for
+ * regions outside 1..VSC_FINE_MAX_REGIONS, fdim outside 1..2^24 (the bound of the identity), packed outside {0, 1} or no
+ * context. */
+int vsc_tn_set_fine_bits(vsc_tn_ctx_t* ctx, const void* qfine, const void* rfine, int regions, int fdim, int packed, int mem);
+/* Bytes the context asked the device for to hold the fine descriptor rows of both sides (cf. vsc_tn_ref_bytes); the
+ * packed bytes for a VSC_FINE_BITS store. */
 int64_t vsc_tn_fine_bytes(const vsc_tn_ctx_t* ctx);
 /* Stage 1: F (steps 1-4) of every pair of the list, row-major lq x lr, at out + out_off[p]; out_off[n_pairs] lies where
  * `out` does (out_mem), cap is the capacity of `out` in floats.  VSC_ERR_CAPACITY with nothing written when a pair does
  * not fit; VSC_ERR_INVALID when a side that has frames has no fine descriptors, or for a pair ordinal outside the
  * context's videos (checked on the host copy of the list and again by the kernel, which skips the tile and raises an
- * error word: nothing is read out of range).  One launch over (pair, tile) work items; stream and synchronisation as
- * vsc_tn_localize. */
+ * error word: nothing is read out of range).  One launch over (pair, tile) work items, of the kernel of the context's
+ * store (fp32 rows on the matrix cores, or bit rows by popcount); stream and synchronisation as vsc_tn_localize. */
 int vsc_tn_fine_similarity(vsc_tn_ctx_t* ctx, const int32_t* pair_q, const int32_t* pair_r, int64_t n_pairs, int pairs_mem,
                            int symmetric, float* out, const int64_t* out_off, int64_t cap, int out_mem);
 /* Stage 2: steps 5-6 for one localize_all batch.  `fine` is a slab of F matrices (stage 1's output or a torch model's),

@@ -16,7 +16,15 @@ Per route one JSON line: wall time (perf_counter; the calls return synchronised)
 the stream the work runs on) of all batches, median and spread over --steps runs after --warmup; stage 1 of the
 chamfer route alone with its TFLOP/s (2 Lq Lr R^2 D flops per pair); the matches of the three routes compared; the box.
 
+--fine_codec bits adds the binary student's leg: the same videos with binary fine descriptors (the sign of the
+projections, as dns_index writes `feature > 0`) through `ChamferSimilarity("bin")` on the device, once with the default
++-1 fp32 store and once with the 1-bit store.  Stage 1 of both is timed in ALTERNATING repetitions in the same process
+(--stage-reps passes over all batches per timing, so that a window is not a fraction of a millisecond of launches);
+one JSON line holds both stores' times and `fine_bytes`, their ratio, and whether the two slabs and the two routes'
+matches are equal bit for bit.  --skip-routes leaves the three att routes out.
+
     python scripts/bench_dns_device.py [--queries 256] [--per-query 8] [--steps 5] [--warmup 1] [--host-steps 2]
+                                       [--fine_codec bits] [--stage-reps 10] [--skip-routes]
 """
 import argparse
 import json
@@ -40,7 +48,7 @@ def box():
     return {"gpu": torch.cuda.get_device_name(0), "cpu": cpu, "host": os.uname().nodename, "torch": torch.__version__}
 
 
-def make_inputs(np, n_query, per_query, regions, fdim, frames=60, dim=512, seed=5):
+def make_inputs(np, n_query, per_query, regions, fdim, frames=60, dim=512, seed=5, binary=False):
     from vsc2022_amd import synth
     from vsc2022_amd.vsc.index import VideoFeature
     from vsc2022_amd.vsc.metrics import CandidatePair
@@ -54,6 +62,8 @@ def make_inputs(np, n_query, per_query, regions, fdim, frames=60, dim=512, seed=
     def fine(v):
         x = np.einsum("ld,rde->lre", np.asarray(v.feature, dtype=np.float32), proj)
         x += 0.05 * rng.standard_normal(x.shape).astype(np.float32)
+        if binary:
+            return VideoFeature(video_id=v.video_id, timestamps=v.timestamps, feature=x > 0)
         return VideoFeature(video_id=v.video_id, timestamps=v.timestamps,
                             feature=(x / np.linalg.norm(x, axis=-1, keepdims=True)).astype(np.float32))
 
@@ -81,8 +91,73 @@ def timed(torch, fn, steps, warmup):
         if step >= warmup:
             wall.append((t1 - t0) * 1e3)
             dev.append(a.elapsed_time(b))
-    stat = lambda x: {"median_ms": round(statistics.median(x), 3), "min_ms": round(min(x), 3), "max_ms": round(max(x), 3), "runs": len(x)}
     return {"wall": stat(wall), "device": stat(dev)}, out
+
+
+def stat(x):
+    return {"median_ms": round(statistics.median(x), 3), "min_ms": round(min(x), 3), "max_ms": round(max(x), 3), "runs": len(x)}
+
+
+def fine_codec_leg(np, torch, args, kw):
+    """The binary student on the device: the +-1 fp32 store against the 1-bit store, stage 1 in alternating repetitions."""
+    from vsc2022_amd.vsc.baseline.dns_baseline import ChamferSimilarity, VCSLLocalizationDnS
+
+    qc, rc, qf, rf, cands = make_inputs(np, args.queries, args.per_query, args.regions, args.fdim, binary=True)
+    model = ChamferSimilarity("bin")
+    locs = {"bin_fp32": VCSLLocalizationDnS(model, qf, rf, qc, rc, on_device=True, **kw),
+            "bits": VCSLLocalizationDnS(model, qf, rf, qc, rc, on_device=True, fine_codec=args.fine_codec, **kw)}
+    parts = [cands[start:start + 512] for start in range(0, len(cands), 512)]
+    flops = 2.0 * sum(len(locs["bits"].queries[c.query_id]) * len(locs["bits"].refs[c.ref_id]) for c in cands) * args.regions ** 2 * args.fdim
+
+    def stage1(loc, keep=False):
+        slabs = []
+        for part in parts:
+            slab, _ = loc._fine_slab(part, *loc._pair_ordinals(part))
+            if keep:
+                slabs.append(slab)
+        return slabs
+
+    torch.cuda.synchronize()
+    slabs = {name: [s.cpu().numpy().view(np.uint32) for s in stage1(loc, keep=True)] for name, loc in locs.items()}
+    same_slabs = all(np.array_equal(a, b) for a, b in zip(slabs["bin_fp32"], slabs["bits"]))
+    wall, dev = {n: [] for n in locs}, {n: [] for n in locs}
+    for step in range(args.warmup + args.steps):
+        for name, loc in locs.items():  # alternating: a drift of the box lands on both
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            a.record()
+            for _ in range(args.stage_reps):
+                stage1(loc)
+            b.record()
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            if step >= args.warmup:
+                wall[name].append((t1 - t0) * 1e3 / args.stage_reps)
+                dev[name].append(a.elapsed_time(b) / args.stage_reps)
+    out = {"stage": "vsc_tn_fine_similarity, binary student", "pairs": len(cands), "batches": len(parts), "regions": args.regions,
+           "fdim": args.fdim, "stage_reps": args.stage_reps, "g_bit_products": round(flops / 2e9, 2), "slabs_equal_bitwise": same_slabs}
+    for name, loc in locs.items():
+        out[name] = {"wall": stat(wall[name]), "device": stat(dev[name]), "fine_bytes": loc.fine_bytes,
+                     "tera_products_per_s_device_median": round(flops / 2 / (statistics.median(dev[name]) * 1e-3) / 1e12, 2)}
+    out["device_time_ratio_fp32_over_bits"] = round(out["bin_fp32"]["device"]["median_ms"] / out["bits"]["device"]["median_ms"], 2)
+    out["fine_bytes_ratio_fp32_over_bits"] = round(out["bin_fp32"]["fine_bytes"] / out["bits"]["fine_bytes"], 2)
+    print(json.dumps(out), flush=True)
+
+    def batches(loc):
+        found = []
+        for part in parts:
+            found += loc.localize_all(part)
+        return found
+
+    res, found = {}, {}
+    for name, loc in locs.items():
+        res[name], found[name] = timed(torch, lambda: batches(loc), args.steps, args.warmup)
+    same = len(found["bits"]) == len(found["bin_fp32"]) and all(
+        a._replace(score=0.0) == b._replace(score=0.0) and np.float32(a.score).view(np.uint32) == np.float32(b.score).view(np.uint32)
+        for a, b in zip(found["bits"], found["bin_fp32"]))
+    print(json.dumps({"route": "device/chamfer, binary student, both stages", "matches": len(found["bits"]),
+                      "matches_equal_bitwise": same, **{name: res[name] for name in locs}, "box": box()}), flush=True)
 
 
 def main():
@@ -94,14 +169,21 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--host-steps", type=int, default=2)
+    ap.add_argument("--fine_codec", choices=["bits"], default=None)
+    ap.add_argument("--stage-reps", type=int, default=10)
+    ap.add_argument("--skip-routes", action="store_true")
     args = ap.parse_args()
     import numpy as np
     import torch
 
     from vsc2022_amd.vsc.baseline.dns_baseline import ChamferSimilarity, VCSLLocalizationDnS
 
-    qc, rc, qf, rf, cands = make_inputs(np, args.queries, args.per_query, args.regions, args.fdim)
     kw = dict(model_type="TN", tn_max_step=5, min_length=4, concurrency=16, similarity_bias=0.5, device="cuda")
+    if args.fine_codec:
+        fine_codec_leg(np, torch, args, kw)
+    if args.skip_routes:
+        return
+    qc, rc, qf, rf, cands = make_inputs(np, args.queries, args.per_query, args.regions, args.fdim)
     model = ChamferSimilarity("att")
     routes = {
         "host": (VCSLLocalizationDnS(model, qf, rf, qc, rc, **kw), args.host_steps, min(args.warmup, 1)),

@@ -1,8 +1,8 @@
 // C ABI of libvscmi.so, part 5: the Temporal-Network localisation contexts (vsc_tn_*), the DTW / DP aligners on them
 // (vsc_tn_align), the handle-less forms of both over caller matrices (vsc_tn_forward_sim, vsc_align_forward_sim), the
 // match-rows stage behind them (vsc_tn_set_timestamps, vsc_tn_match_rows) and the DnS fine descriptors (vsc_tn_set_fine,
-// vsc_tn_fine_similarity, vsc_tn_localize_fine, vsc_tn_similarity_fine).  Host plumbing only: the kernels are in tn.hip,
-// align.hip, match_rows.hip and fine_sim.hip.
+// vsc_tn_set_fine_bits, vsc_tn_fine_similarity, vsc_tn_localize_fine, vsc_tn_similarity_fine).  Host plumbing only: the
+// kernels are in tn.hip, align.hip, match_rows.hip, fine_sim.hip and fine_bits.hip.
 #include "api_internal.h"
 
 // ------------------------------------------------------------------------ TN launches
@@ -251,9 +251,10 @@ struct vsc_tn_ctx {
     DevBuf d_qts, d_rts, d_rowoff, d_tileoff, d_rowctl, d_rows[4];
     bool has_qts = false, has_rts = false;
     // DnS fine descriptors (vsc_tn_set_fine): fine_regions packed fp32 rows of fine_dpad floats per frame of either side
-    // (bin: +-1), the scratch of vsc_tn_fine_similarity (work list, offsets, error word, dense output for host callers)
+    // (bin: +-1) -- or, fine_kind == VSC_FINE_BITS (vsc_tn_set_fine_bits), bit rows of fine_w16 16-byte words in the same
+    // buffers --, the scratch of vsc_tn_fine_similarity (work list, offsets, error word, dense output for host callers)
     // and of vsc_tn_localize_fine / vsc_tn_similarity_fine (the fine slab of host callers, its offsets, frame counts)
-    int fine_regions = 0, fine_dim = 0, fine_dpad = 0, fine_kind = -1;
+    int fine_regions = 0, fine_dim = 0, fine_dpad = 0, fine_w16 = 0, fine_kind = -1;
     bool has_qfine = false, has_rfine = false;
     int64_t qfine_bytes = 0, rfine_bytes = 0;
     DevBuf qfine, rfine, d_fwork, d_foff, d_ferr, fine_out, fine_mat, d_flq, d_flr;
@@ -932,6 +933,63 @@ int vsc_tn_set_fine(vsc_tn_ctx_t* c, const void* qfine, const void* rfine, int r
     return VSC_OK;
 }
 
+// One side's bit rows (VSC_FINE_BITS): `rows` source rows -- fine_dim bytes {0, 1} each, or ceil(fine_dim / 8) packed
+// bytes -- -> rows_out rows of fine_w16 16-byte words at dst, those from `rows` on as zeros.  Host sources are staged in
+// chunks of <= 64 MB (ws.stage); a chunk is one launch.
+static int tn_fine_store_bits(vsc_tn_ctx* c, const void* x, bool packed, int64_t rows, int mem, uint32_t* dst, int64_t rows_out) {
+    const int dim = c->fine_dim, w16 = c->fine_w16;
+    const int64_t src_row = packed ? (dim + 7) / 8 : dim;
+    const int64_t chunk_rows = std::max<int64_t>(1, (int64_t)(64ll << 20) / std::max<int64_t>(src_row, 16 * (int64_t)w16));
+    const bool host = mem != VSC_MEM_DEVICE;
+    if (host && rows > 0) VSC_TRY(c->ws.stage.reserve((size_t)(std::min(chunk_rows, rows) * src_row)));
+    for (int64_t r0 = 0; r0 < rows_out; r0 += chunk_rows) {
+        const int64_t n_out = std::min(chunk_rows, rows_out - r0);
+        const int64_t n = std::max<int64_t>(0, std::min(n_out, rows - r0));  // source rows of the chunk
+        const void* src = n ? static_cast<const char*>(x) + (size_t)(r0 * src_row) : nullptr;
+        if (host && n) {
+            VSC_HIP(hipMemcpyAsync(c->ws.stage.p, src, (size_t)(n * src_row), hipMemcpyHostToDevice, c->stream));
+            src = c->ws.stage.p;
+        }
+        VSC_TRY(launch_pack_bits(static_cast<const uint8_t*>(src), packed, n, dim, dst + r0 * 4 * w16, n_out, w16, c->stream));
+        if (host && n) VSC_HIP(hipStreamSynchronize(c->stream));  // the staging buffer is reused
+    }
+    return VSC_OK;
+}
+
+int vsc_tn_set_fine_bits(vsc_tn_ctx_t* c, const void* qfine, const void* rfine, int regions, int fdim, int packed, int mem) {
+    if (!c || regions < 1 || regions > VSC_FINE_MAX_REGIONS || fdim < 1 || fdim > (1 << 24) || (packed != 0 && packed != 1)) {
+        set_error("vsc_tn_set_fine_bits: invalid argument (regions 1..%d, fdim 1..%d, packed 0 / 1)", VSC_FINE_MAX_REGIONS, 1 << 24);
+        return VSC_ERR_INVALID;
+    }
+    VSC_HIP(hipSetDevice(c->device));
+    if (regions != c->fine_regions || fdim != c->fine_dim || c->fine_kind != VSC_FINE_BITS) {
+        // (as vsc_tn_set_fine: a side kept from another shape or kind could not meet the new one)
+        c->has_qfine = c->has_rfine = false;
+        c->qfine_bytes = c->rfine_bytes = 0;
+    }
+    c->fine_regions = regions;
+    c->fine_dim = fdim;
+    c->fine_kind = VSC_FINE_BITS;
+    c->fine_dpad = 0;
+    c->fine_w16 = fine_bits_row_words(fdim);
+    struct Side { const void* x; int64_t frames; DevBuf* buf; bool* has; int64_t* bytes; };
+    Side sides[2] = {{qfine, c->q_off.back(), &c->qfine, &c->has_qfine, &c->qfine_bytes},
+                     {rfine, c->r_off.back(), &c->rfine, &c->has_rfine, &c->rfine_bytes}};
+    for (Side& s : sides) {
+        if (!s.x) continue;
+        *s.has = false;  // (until the new rows are down)
+        const int64_t rows = s.frames * regions;
+        // +64 rows of slack, zeroed: the 64-row tiles of the last video's last frames read past its end (fine_bits.hip)
+        const int64_t rows_out = round_up64(rows + 64, ROW_PAD);
+        VSC_TRY(s.buf->reserve((size_t)rows_out * c->fine_w16 * 16));
+        VSC_TRY(tn_fine_store_bits(c, s.x, packed != 0, rows, mem, s.buf->as<uint32_t>(), rows_out));
+        *s.bytes = rows_out * c->fine_w16 * 16;
+        *s.has = true;
+    }
+    VSC_HIP(hipStreamSynchronize(c->stream));
+    return VSC_OK;
+}
+
 int64_t vsc_tn_fine_bytes(const vsc_tn_ctx_t* c) { return c ? c->qfine_bytes + c->rfine_bytes : 0; }
 
 int vsc_tn_fine_similarity(vsc_tn_ctx_t* c, const int32_t* pair_q, const int32_t* pair_r, int64_t n_pairs, int pairs_mem,
@@ -996,35 +1054,49 @@ int vsc_tn_fine_similarity(vsc_tn_ctx_t* c, const int32_t* pair_q, const int32_t
     VSC_TRY(c->d_ferr.reserve(16));
     VSC_HIP(hipMemcpyAsync(c->d_fwork.p, work.data(), work.size() * 4, hipMemcpyHostToDevice, c->stream));
     VSC_HIP(hipMemsetAsync(c->d_ferr.p, 0, sizeof(int), c->stream));
-    FineSimArgs a;
-    memset(&a, 0, sizeof(a));
-    a.qfine = c->qfine.as<float>();
-    a.rfine = c->rfine.as<float>();
-    a.q_off = c->d_qoff.as<int64_t>();
-    a.r_off = c->d_roff.as<int64_t>();
-    a.n_qvid = c->n_qvid;
-    a.n_rvid = c->n_rvid;
-    a.pair_q = c->d_pq.as<int32_t>();
-    a.pair_r = c->d_pr.as<int32_t>();
-    a.work = c->d_fwork.as<int32_t>();
-    a.n_work = (int)n_work;
-    a.regions = c->fine_regions;
-    a.fdim = c->fine_dim;
-    a.dpad = c->fine_dpad;
-    a.bin = c->fine_kind == VSC_FINE_BIN;
-    a.symmetric = symmetric != 0;
-    a.err = c->d_ferr.as<int>();
+    float* d_out = out;
+    const int64_t* d_off = out_off;
     if (out_mem == VSC_MEM_HOST) {
         VSC_TRY(c->fine_out.reserve((size_t)total * 4));
         VSC_TRY(c->d_foff.reserve((size_t)n_pairs * 8));
         VSC_HIP(hipMemcpyAsync(c->d_foff.p, dense.data(), (size_t)n_pairs * 8, hipMemcpyHostToDevice, c->stream));
-        a.out = c->fine_out.as<float>();
-        a.out_off = c->d_foff.as<int64_t>();
-    } else {
-        a.out = out;
-        a.out_off = out_off;
+        d_out = c->fine_out.as<float>();
+        d_off = c->d_foff.as<int64_t>();
     }
-    VSC_TRY(launch_fine_sim(a, c->stream));
+    // what both kernels' argument blocks name alike (kernels.h)
+    auto bind = [&](auto& a) {
+        memset(&a, 0, sizeof(a));
+        a.q_off = c->d_qoff.as<int64_t>();
+        a.r_off = c->d_roff.as<int64_t>();
+        a.n_qvid = c->n_qvid;
+        a.n_rvid = c->n_rvid;
+        a.pair_q = c->d_pq.as<int32_t>();
+        a.pair_r = c->d_pr.as<int32_t>();
+        a.work = c->d_fwork.as<int32_t>();
+        a.n_work = (int)n_work;
+        a.regions = c->fine_regions;
+        a.fdim = c->fine_dim;
+        a.symmetric = symmetric != 0;
+        a.err = c->d_ferr.as<int>();
+        a.out = d_out;
+        a.out_off = d_off;
+    };
+    if (c->fine_kind == VSC_FINE_BITS) {
+        FineBitsArgs a;
+        bind(a);
+        a.qbits = c->qfine.as<uint4>();
+        a.rbits = c->rfine.as<uint4>();
+        a.w16 = c->fine_w16;
+        VSC_TRY(launch_fine_bits(a, c->stream));
+    } else {
+        FineSimArgs a;
+        bind(a);
+        a.qfine = c->qfine.as<float>();
+        a.rfine = c->rfine.as<float>();
+        a.dpad = c->fine_dpad;
+        a.bin = c->fine_kind == VSC_FINE_BIN;
+        VSC_TRY(launch_fine_sim(a, c->stream));
+    }
     int err = 0;
     VSC_HIP(hipMemcpyAsync(&err, c->d_ferr.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     std::vector<float> back;

@@ -19,15 +19,16 @@
 // Bound: matrix cores.  2 Lq Lr R^2 D flops per pair against 4 D R (Lq + Lr) bytes of region rows read once from HBM and
 // 4 Lq Lr bytes written: 0.3 GFLOP against 2.2 MB at 60 x 60 frames, R = 9, D = 512 (135 flop / byte; the exact fp32
 // similarity kernel reaches 137 TFLOP/s).  Every tile re-reads its rows from L2 (no operand staging in LDS) and a
-// quarter of the lanes idle in the reductions at R = 16 -- UNMEASURED until profiles/dns_device.md holds a run of
-// scripts/bench_dns_device.py.
+// quarter of the lanes idle in the reductions at R = 16.  Measured at that shape (profiles/dns_device.md): 58 TFLOP/s.
+//
+// VSC_FINE_BIN rows are +-1 fp32 here (the chain's result divided once by the width).  The 1-bit store of the same
+// descriptors (VSC_FINE_BITS) has its own step 1 in fine_bits.hip -- xor + popcount, the same bits -- and shares steps
+// 2-4 with this kernel through fine_chamfer.h (FS_TILE = 64 region rows / columns per work item: 2 x 2 MFMA blocks here).
+#include "fine_chamfer.h"
 #include "kernels.h"
 #include "tn_sims.h"
 
 namespace vscmi {
-
-constexpr int FS_TILE = 64;  // region rows / columns of one work item (2 x 2 MFMA blocks)
-constexpr int FS_LD = 65;    // leading dimension of the LDS piece (odd: the column walks of the backward maxima spread over banks)
 
 int fine_sim_frames(int regions) { return FS_TILE / regions; }
 
@@ -74,45 +75,8 @@ __global__ __launch_bounds__(256) void fine_sim_kernel(FineSimArgs a) {
     }
     __syncthreads();
 
-    // ---- 2. maxima: one lane per (frame pair, region) ----
-    const int nfp = nfq * nfr;
-    for (int x = tid; x < nfp * R; x += 256) {
-        const int fp = x / R, c = x - fp * R;
-        const int i = fp / nfr, j = fp - i * nfr;
-        const float* g = G + (i * R + c) * FS_LD + j * R;  // region c of query frame i against the regions of frame j
-        float m = g[0];
-        for (int b = 1; b < R; ++b) {
-            const float v = g[b];
-            m = v > m ? v : m;
-        }
-        fwd[x] = m;
-        if (a.symmetric) {
-            const float* h = G + (i * R) * FS_LD + j * R + c;  // region c of reference frame j against the regions of frame i
-            float m2 = h[0];
-            for (int b = 1; b < R; ++b) {
-                const float v = h[b * FS_LD];
-                m2 = v > m2 ? v : m2;
-            }
-            bwd[x] = m2;
-        }
-    }
-    __syncthreads();
-
-    // ---- 3. sums in region order, the mapping to [0, 1]: one lane per frame pair ----
-    const float regions = (float)R;
-    float* out = a.out + a.out_off[p];
-    for (int x = tid; x < nfp; x += 256) {
-        const int i = x / nfr, j = x - i * nfr;
-        float t = 0.0f;
-        for (int c = 0; c < R; ++c) t = __fadd_rn(t, fwd[x * R + c]);
-        float f0 = __fdiv_rn(t, regions);
-        if (a.symmetric) {
-            float u = 0.0f;
-            for (int c = 0; c < R; ++c) u = __fadd_rn(u, bwd[x * R + c]);
-            f0 = __fdiv_rn(__fadd_rn(f0, __fdiv_rn(u, regions)), 2.0f);
-        }
-        out[(int64_t)(qf0 + i) * lr + rf0 + j] = __fadd_rn(__fdiv_rn(f0, 2.0f), 0.5f);
-    }
+    // ---- 2-4. maxima, sums in region order, the mapping to [0, 1] (fine_chamfer.h) ----
+    fine_chamfer_reduce(G, fwd, bwd, tid, R, nfq, nfr, a.symmetric, a.out, a.out_off, p, lr, qf0, rf0);
 }
 
 int launch_fine_sim(const FineSimArgs& a, hipStream_t stream) {

@@ -198,6 +198,16 @@ struct FineSimArgs {
     float* out; const int64_t* out_off;  // F of pair p, row-major lq x lr, at out + out_off[p]
     int* err;  // error word: bit 0 = a pair ordinal outside the context's videos (that work item is skipped)
 };
+// The same on the 1-bit store (fine_bits.hip, VSC_FINE_BITS): FineSimArgs' fields under FineSimArgs' names, the rows as bits
+struct FineBitsArgs {
+    const uint4* qbits; const uint4* rbits;  // bit rows, regions rows per frame, w16 16-byte words each (zero past fdim)
+    const int64_t* q_off; const int64_t* r_off; int64_t n_qvid, n_rvid;
+    const int32_t* pair_q; const int32_t* pair_r;
+    const int32_t* work; int n_work;
+    int regions, fdim, w16, symmetric;
+    float* out; const int64_t* out_off;
+    int* err;
+};
 
 // DTW / DP aligners (align.hip): one candidate pair per single-wavefront workgroup, as tn_pair_kernel; the fields the
 // similarity tile reads (tn_sims.h) carry TnPairArgs' names
@@ -352,6 +362,9 @@ int launch_tn_sims(const TnSimsArgs&, hipStream_t);
 int fine_sim_frames(int regions);  // frames per side of a work item of launch_fine_sim
 int launch_fine_sim(const FineSimArgs&, hipStream_t);
 int launch_bin_to_pm1(const uint8_t*, int64_t, float*, hipStream_t);
+int fine_bits_row_words(int fdim);  // 16-byte words of one bit row (fine_bits.hip)
+int launch_fine_bits(const FineBitsArgs&, hipStream_t);
+int launch_pack_bits(const uint8_t*, bool, int64_t, int, uint32_t*, int64_t, int, hipStream_t);
 int launch_align_pairs(const AlignArgs&, size_t, hipStream_t);
 int64_t match_rows_tiles(int64_t n_pairs);
 int launch_match_rows_scan(const MatchRowsArgs&, hipStream_t);

@@ -26,6 +26,11 @@ pair, on `torch_device` (a GPU), with its descriptors uploaded once per unique v
 scores; nothing is copied to the host before the box table.  The arithmetic is written down in include/vscmi.h ("DnS
 localisation on the device"): with a torch model both routes see the same F bits and return equal matches; with
 `ChamferSimilarity` the device route has the bits of the CPU restatement in tests/dns_fine_ref.py.
+
+`fine_codec="bits"` (with on_device=True and `ChamferSimilarity("bin")` only) keeps the binary student's descriptors in
+HBM as the bits they are, 1/32 of the default +-1 fp32 rows: each video is packed on the host
+(`pack_fine_bits`), `vsc_tn_set_fine_bits` stores the rows and stage 1 runs on xor + popcount (fine_bits.hip).  The
+results are the bits of the default store: include/vscmi.h writes down why.
 """
 import argparse
 import ctypes
@@ -57,6 +62,28 @@ def _by_id(features: FineFeatures) -> Dict[object, VideoFeature]:
     return {v.video_id: v for v in features}
 
 
+FINE_CODECS = ("bits",)
+
+
+def pack_fine_bits(feature) -> np.ndarray:
+    """Binary fine descriptors [..., D] (bool, or integers {0, 1}) -> [..., ceil(D / 8)] bytes, element d in bit d % 8 of
+    byte d / 8: the packed input of `vsc_tn_set_fine_bits`."""
+    return np.packbits(np.asarray(feature) > 0, axis=-1, bitorder="little")
+
+
+def _check_fine_codec(fine_codec, on_device: bool, model):
+    """What `fine_codec` can be asked for, judged before anything touches a device."""
+    if fine_codec is None:
+        return
+    if fine_codec not in FINE_CODECS:
+        raise ValueError(f"unknown fine_codec {fine_codec!r} (None or one of {FINE_CODECS})")
+    if not on_device:
+        raise ValueError(f"fine_codec={fine_codec!r} is a store of the device route: it needs on_device=True")
+    if type(model) is not ChamferSimilarity or "bin" not in getattr(model, "fg_type", ""):
+        raise ValueError(f"fine_codec={fine_codec!r} packs binary descriptors for libvscmi's region Chamfer kernel: the model "
+                         "must be exactly ChamferSimilarity with \"bin\" in fg_type")
+
+
 class ChamferSimilarity(torch.nn.Module):
     """The ViSiL / DnS frame-to-frame region Chamfer similarity, the part of a fine-grained student that has no weights:
     inner products of all region pairs of two frames, max over the second argument's regions, mean over the first's.
@@ -79,11 +106,13 @@ class ChamferSimilarity(torch.nn.Module):
 class VCSLLocalizationDnS(VCSLLocalizationMaxSim):
     def __init__(self, model, queries_fine: FineFeatures, refs_fine: FineFeatures,
                  queries_coarse: List[VideoFeature], refs_coarse: List[VideoFeature], model_type, device,
-                 symmetric: bool = True, geometric_mean: bool = True, on_device: bool = False, **kwargs):
+                 symmetric: bool = True, geometric_mean: bool = True, on_device: bool = False, fine_codec=None, **kwargs):
         # the reference stores what it was given (a torch.device or the --accelerator string) and only ever hands it
         # to Tensor.to(); "cuda" is the ROCm device under PyTorch-ROCm
         torch_device = device if isinstance(device, torch.device) else torch.device(device)
         self._chamfer = type(model) is ChamferSimilarity
+        _check_fine_codec(fine_codec, bool(on_device), model)
+        self.fine_codec = fine_codec
         if on_device:  # (checked before the descriptors go anywhere)
             if model_type != "TN":
                 raise ValueError(f"on_device=True aligns with the Temporal Network kernel: model_type {model_type!r} is not \"TN\"")
@@ -108,8 +137,11 @@ class VCSLLocalizationDnS(VCSLLocalizationMaxSim):
 
     # -- on_device=True ----------------------------------------------------------------------------
     def _upload_fine(self):
-        """The fine descriptors of both sides, in the order of the context's videos, down once (vsc_tn_set_fine)."""
+        """The fine descriptors of both sides, in the order of the context's videos, down once (vsc_tn_set_fine; with
+        fine_codec="bits" packed video by video first, so that the host staging copy is D / 8 bytes per region, and
+        handed to vsc_tn_set_fine_bits)."""
         binary = "bin" in self.sim_model.fg_type
+        bits = self.fine_codec == "bits"
         sides = []
         for videos, table in ((self._q_videos, self.queries_fine), (self._r_videos, self.refs_fine)):
             parts = []
@@ -117,20 +149,22 @@ class VCSLLocalizationDnS(VCSLLocalizationMaxSim):
                 x = np.asarray(table[v.video_id].feature)
                 if x.ndim != 3 or len(x) != len(v):
                     raise ValueError(f"video {v.video_id!r}: fine descriptors of shape {x.shape} for {len(v)} frames ([L, R, D] expected)")
-                parts.append(x)
+                parts.append((x.shape[1:], pack_fine_bits(x)) if bits else (x.shape[1:], x))
             sides.append(parts)
-        shapes = {p.shape[1:] for parts in sides for p in parts}
+        shapes = {shape for parts in sides for shape, _ in parts}
         if len(shapes) > 1:
             raise ValueError(f"fine descriptors differ in regions x width: {sorted(shapes)}")
         if not shapes:
             return
         regions, width = shapes.pop()
-        rows = [np.ascontiguousarray(np.concatenate(parts, axis=0), dtype=np.uint8 if binary else np.float32) if parts else None
-                for parts in sides]
-        _lib.check(_lib.lib().vsc_tn_set_fine(
-            self._ctx, rows[0].ctypes.data if rows[0] is not None and rows[0].size else None,
-            rows[1].ctypes.data if rows[1] is not None and rows[1].size else None, int(regions), int(width),
-            _lib.FINE_BIN if binary else _lib.FINE_ATT, _lib.MEM_HOST))
+        rows = [np.ascontiguousarray(np.concatenate([x for _, x in parts], axis=0), dtype=np.uint8 if binary else np.float32)
+                if parts else None for parts in sides]
+        addr = [x.ctypes.data if x is not None and x.size else None for x in rows]
+        if bits:
+            _lib.check(_lib.lib().vsc_tn_set_fine_bits(self._ctx, addr[0], addr[1], int(regions), int(width), 1, _lib.MEM_HOST))
+        else:
+            _lib.check(_lib.lib().vsc_tn_set_fine(self._ctx, addr[0], addr[1], int(regions), int(width),
+                                                  _lib.FINE_BIN if binary else _lib.FINE_ATT, _lib.MEM_HOST))
 
     @property
     def fine_bytes(self) -> int:
@@ -275,13 +309,13 @@ def search(queries: List[VideoFeature], refs: List[VideoFeature], retrieve_per_q
 
 def localize_and_verify(model, queries_fine: FineFeatures, refs_fine: FineFeatures, queries_coarse: List[VideoFeature],
                         refs_coarse: List[VideoFeature], candidates: Sequence[CandidatePair],
-                        localize_per_query: float = 5.0, device="cpu", on_device: bool = False) -> List[Match]:
+                        localize_per_query: float = 5.0, device="cpu", on_device: bool = False, fine_codec=None) -> List[Match]:
     """Reference :183-227: the best `localize_per_query * len(queries_fine)` candidates, batches of 512 pairs.
-    on_device: `VCSLLocalizationDnS(on_device=True)`, every matrix stays in HBM."""
+    on_device: `VCSLLocalizationDnS(on_device=True)`, every matrix stays in HBM; fine_codec: its store of the fine rows."""
     todo = candidates[: int(len(queries_fine) * localize_per_query)]
     aligner = VCSLLocalizationDnS(model, queries_fine, refs_fine, queries_coarse, refs_coarse, model_type="TN",
                                   tn_max_step=5, min_length=4, concurrency=16, similarity_bias=0.5, device=device,
-                                  on_device=on_device)
+                                  on_device=on_device, fine_codec=fine_codec)
     found: List[Match] = []
     batch = 512
     for start in range(0, len(todo), batch):
@@ -291,14 +325,15 @@ def localize_and_verify(model, queries_fine: FineFeatures, refs_fine: FineFeatur
 
 
 def match(model, queries_fine: FineFeatures, refs_fine: FineFeatures, queries_coarse: List[VideoFeature],
-          refs_coarse: List[VideoFeature], output_path: str, device, on_device: bool = False) -> Tuple[str, str]:
+          refs_coarse: List[VideoFeature], output_path: str, device, on_device: bool = False,
+          fine_codec=None) -> Tuple[str, str]:
     """Reference :230-258; returns the paths of candidates.csv and matches.csv."""
     pairs = search(queries_coarse, refs_coarse)
     os.makedirs(output_path, exist_ok=True)
     candidate_file = os.path.join(output_path, "candidates.csv")
     CandidatePair.write_csv(pairs, candidate_file)
     found = localize_and_verify(model, queries_fine, refs_fine, queries_coarse, refs_coarse, pairs, device=device,
-                                on_device=on_device)
+                                on_device=on_device, fine_codec=fine_codec)
     matches_file = os.path.join(output_path, "matches.csv")
     Match.write_csv(found, matches_file)
     return candidate_file, matches_file
@@ -319,6 +354,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--overwrite", help="Overwrite prediction files, if found.", action="store_true")
     p.add_argument("--on_device", help="Keep the similarity matrices of the localisation in HBM (needs a GPU accelerator).",
                    action="store_true")
+    p.add_argument("--fine_codec", help="Store of the fine descriptors in HBM with --on_device: bits = 1 bit per value "
+                   "(binary students through ChamferSimilarity only).", choices=list(FINE_CODECS), default=None)
     return p
 
 
@@ -326,6 +363,8 @@ parser = build_parser()
 
 
 def main(args):
+    if getattr(args, "fine_codec", None) is not None and not args.on_device:
+        raise ValueError("--fine_codec is a store of the device route: it needs --on_device")
     if os.path.exists(args.output_path) and not args.overwrite:
         raise Exception(f"Output path already exists: {args.output_path}. Do you want to --overwrite?")
     model = torch.jit.load(args.torchscript_path)
@@ -338,7 +377,7 @@ def main(args):
     queries_coarse = storage.load_features(args.query_coarse_features, M.Dataset.QUERIES)
     refs_coarse = storage.load_features(args.ref_coarse_features, M.Dataset.REFS)
     candidate_file, match_file = match(model, queries_fine, refs_fine, queries_coarse, refs_coarse, args.output_path,
-                                       device, on_device=args.on_device)
+                                       device, on_device=args.on_device, fine_codec=getattr(args, "fine_codec", None))
     if args.ground_truth:
         from vsc2022_amd.vsc.baseline.sscd_baseline import _report
 
