@@ -472,10 +472,28 @@ int vsc_tn_similarity(vsc_tn_ctx_t* ctx, int32_t q_vid, int32_t r_vid, float bia
  *            are zero on BOTH sides: they xor to zero and never enter a popcount (D in the formula is the true fdim).
  *            64 zero rows of slack follow a side's last frame, as in the fp32 store.
  *   masking  packed input carries ceil(D / 8) bytes per row; the unused high bits of a row's last byte are the caller's:
- *            the library masks them, whatever they hold changes no result. */
+ *            the library masks them, whatever they hold changes no result.
+ *
+ * The half-float store (VSC_FINE_F16, vsc_tn_set_fine_f16) keeps ATT descriptors as IEEE half floats, which is what the
+ * DnS indexer writes for an attention student (feature.half()).  With dec(X) = (float)(half)X -- the index codec's
+ * encoder: round to nearest even, subnormals kept -- a context whose descriptors X are in this store returns the BITS
+ * that the VSC_FINE_ATT store returns on dec(X), in step 1 and therefore in everything downstream of it: a half
+ * converts to fp32 exactly (the hardware conversion, in registers), the same values enter the same chain from +0 in
+ * the same ascending order, and steps 2-6 are the same code.  Half-float inputs decode to themselves: their results
+ * are those of the VSC_FINE_ATT store on the same descriptors, at half of its memory and half of the transfer.  No
+ * product or sum is ever formed in half precision.
+ *   layout   one row per (frame, region) of fdim halves padded with zeros to a multiple of 64, natural k order (each
+ *            lane half of the kernel loads a 16-byte piece and keeps its 4 of the 8 values); 64 zero rows of slack
+ *            follow a side's last frame, rows padded to a multiple of 128 as in the fp32 store: vsc_tn_fine_bytes is
+ *            round_up(frames R + 64, 128) * round_up(fdim, 64) * 2 per side, exactly half of the VSC_FINE_ATT figure.
+ *   refusal  a source element that is NaN, +-inf or of magnitude beyond 65504 (fp32 source), or a half holding inf or
+ *            NaN (half source), is VSC_ERR_INVALID -- the index codec's rule.  The side being written is then DROPPED
+ *            (the context holds no descriptors and no bytes for it), the other side is untouched, and
+ *            vsc_tn_fine_similarity refuses until the side is set again: a half-written side is never readable. */
 #define VSC_FINE_ATT 0
 #define VSC_FINE_BIN 1
 #define VSC_FINE_BITS 2 /* a context state only (vsc_tn_set_fine_bits): vsc_tn_set_fine refuses it as an unknown kind */
+#define VSC_FINE_F16 3  /* a context state only, like VSC_FINE_BITS (vsc_tn_set_fine_f16): vsc_tn_set_fine refuses it */
 #define VSC_FINE_MAX_REGIONS 16
 /* Attach fine descriptors to a context: qfine / rfine = [total frames of that side][regions][fdim] in `mem` (host or
  * device; host sources are staged in chunks), fp32 (ATT) or bytes (BIN); the frame counts and video offsets are the
@@ -493,15 +511,23 @@ int vsc_tn_set_fine(vsc_tn_ctx_t* ctx, const void* qfine, const void* rfine, int
  * regions outside 1..VSC_FINE_MAX_REGIONS, fdim outside 1..2^24 (the bound of the identity), packed outside {0, 1} or no
  * context. */
 int vsc_tn_set_fine_bits(vsc_tn_ctx_t* ctx, const void* qfine, const void* rfine, int regions, int fdim, int packed, int mem);
+/* Attach ATT descriptors to a context as half floats (the VSC_FINE_F16 store above).  src_f16 = 0: the input of
+ * VSC_FINE_ATT, fp32 [frames][regions][fdim], rounded here; src_f16 = 1: IEEE halves of the same shape, taken as they
+ * are (no fp32 copy of them exists at any time).  `mem`, a NULL side, changed regions / fdim, and vsc_tn_set_queries as
+ * for vsc_tn_set_fine; going from an ATT / BIN / BITS store to this one or back drops both sides first.
+ * vsc_tn_fine_similarity then runs the region Chamfer kernel on half rows; every other call is unchanged.
+ * VSC_ERR_INVALID for regions outside 1..VSC_FINE_MAX_REGIONS, fdim < 1, src_f16 outside {0, 1} or no context (judged
+ * before the context is read), and for a source element a half cannot hold (see "refusal" above: that side is dropped). */
+int vsc_tn_set_fine_f16(vsc_tn_ctx_t* ctx, const void* qfine, const void* rfine, int regions, int fdim, int src_f16, int mem);
 /* Bytes the context asked the device for to hold the fine descriptor rows of both sides (cf. vsc_tn_ref_bytes); the
- * packed bytes for a VSC_FINE_BITS store. */
+ * packed bytes for a VSC_FINE_BITS store, the half-float bytes for a VSC_FINE_F16 store. */
 int64_t vsc_tn_fine_bytes(const vsc_tn_ctx_t* ctx);
 /* Stage 1: F (steps 1-4) of every pair of the list, row-major lq x lr, at out + out_off[p]; out_off[n_pairs] lies where
  * `out` does (out_mem), cap is the capacity of `out` in floats.  VSC_ERR_CAPACITY with nothing written when a pair does
  * not fit; VSC_ERR_INVALID when a side that has frames has no fine descriptors, or for a pair ordinal outside the
  * context's videos (checked on the host copy of the list and again by the kernel, which skips the tile and raises an
  * error word: nothing is read out of range).  One launch over (pair, tile) work items, of the kernel of the context's
- * store (fp32 rows on the matrix cores, or bit rows by popcount); stream and synchronisation as vsc_tn_localize. */
+ * store (fp32 or half-float rows on the matrix cores, or bit rows by popcount); stream and synchronisation as vsc_tn_localize. */
 int vsc_tn_fine_similarity(vsc_tn_ctx_t* ctx, const int32_t* pair_q, const int32_t* pair_r, int64_t n_pairs, int pairs_mem,
                            int symmetric, float* out, const int64_t* out_off, int64_t cap, int out_mem);
 /* Stage 2: steps 5-6 for one localize_all batch.  `fine` is a slab of F matrices (stage 1's output or a torch model's),

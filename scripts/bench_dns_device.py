@@ -23,8 +23,13 @@ projections, as dns_index writes `feature > 0`) through `ChamferSimilarity("bin"
 one JSON line holds both stores' times and `fine_bytes`, their ratio, and whether the two slabs and the two routes'
 matches are equal bit for bit.  --skip-routes leaves the three att routes out.
 
+--fine_codec SQfp16 adds the attention student's leg in the same way: the same videos with the fine descriptors cast to
+float16 (what dns_index writes for an attention student) through `ChamferSimilarity("att")` on the device, once with the
+default fp32 store and once with the half-float store.  Besides the above the line holds the fp32 store's own spread,
+(max - min) / median of its stage-1 device times, and whether the half store's median stays within it.
+
     python scripts/bench_dns_device.py [--queries 256] [--per-query 8] [--steps 5] [--warmup 1] [--host-steps 2]
-                                       [--fine_codec bits] [--stage-reps 10] [--skip-routes]
+                                       [--fine_codec bits|SQfp16] [--stage-reps 10] [--skip-routes]
 """
 import argparse
 import json
@@ -99,15 +104,22 @@ def stat(x):
 
 
 def fine_codec_leg(np, torch, args, kw):
-    """The binary student on the device: the +-1 fp32 store against the 1-bit store, stage 1 in alternating repetitions."""
+    """A student on the device, the default fp32 store against `--fine_codec`'s store, stage 1 in alternating repetitions:
+    the binary student (+-1 fp32 against bits) or the attention student on float16 descriptors (fp32 against halves)."""
     from vsc2022_amd.vsc.baseline.dns_baseline import ChamferSimilarity, VCSLLocalizationDnS
+    from vsc2022_amd.vsc.index import VideoFeature
 
-    qc, rc, qf, rf, cands = make_inputs(np, args.queries, args.per_query, args.regions, args.fdim, binary=True)
-    model = ChamferSimilarity("bin")
-    locs = {"bin_fp32": VCSLLocalizationDnS(model, qf, rf, qc, rc, on_device=True, **kw),
-            "bits": VCSLLocalizationDnS(model, qf, rf, qc, rc, on_device=True, fine_codec=args.fine_codec, **kw)}
+    binary = args.fine_codec == "bits"
+    plain, coded = ("bin_fp32", "bits") if binary else ("att_fp32", "att_f16")
+    qc, rc, qf, rf, cands = make_inputs(np, args.queries, args.per_query, args.regions, args.fdim, binary=binary)
+    if not binary:
+        qf, rf = ([VideoFeature(video_id=v.video_id, timestamps=v.timestamps, feature=v.feature.astype(np.float16)) for v in side]
+                  for side in (qf, rf))
+    model = ChamferSimilarity("bin" if binary else "att")
+    locs = {plain: VCSLLocalizationDnS(model, qf, rf, qc, rc, on_device=True, **kw),
+            coded: VCSLLocalizationDnS(model, qf, rf, qc, rc, on_device=True, fine_codec=args.fine_codec, **kw)}
     parts = [cands[start:start + 512] for start in range(0, len(cands), 512)]
-    flops = 2.0 * sum(len(locs["bits"].queries[c.query_id]) * len(locs["bits"].refs[c.ref_id]) for c in cands) * args.regions ** 2 * args.fdim
+    flops = 2.0 * sum(len(locs[coded].queries[c.query_id]) * len(locs[coded].refs[c.ref_id]) for c in cands) * args.regions ** 2 * args.fdim
 
     def stage1(loc, keep=False):
         slabs = []
@@ -119,7 +131,7 @@ def fine_codec_leg(np, torch, args, kw):
 
     torch.cuda.synchronize()
     slabs = {name: [s.cpu().numpy().view(np.uint32) for s in stage1(loc, keep=True)] for name, loc in locs.items()}
-    same_slabs = all(np.array_equal(a, b) for a, b in zip(slabs["bin_fp32"], slabs["bits"]))
+    same_slabs = all(np.array_equal(a, b) for a, b in zip(slabs[plain], slabs[coded]))
     wall, dev = {n: [] for n in locs}, {n: [] for n in locs}
     for step in range(args.warmup + args.steps):
         for name, loc in locs.items():  # alternating: a drift of the box lands on both
@@ -135,13 +147,21 @@ def fine_codec_leg(np, torch, args, kw):
             if step >= args.warmup:
                 wall[name].append((t1 - t0) * 1e3 / args.stage_reps)
                 dev[name].append(a.elapsed_time(b) / args.stage_reps)
-    out = {"stage": "vsc_tn_fine_similarity, binary student", "pairs": len(cands), "batches": len(parts), "regions": args.regions,
-           "fdim": args.fdim, "stage_reps": args.stage_reps, "g_bit_products": round(flops / 2e9, 2), "slabs_equal_bitwise": same_slabs}
+    student = "binary" if binary else "attention"
+    out = {"stage": "vsc_tn_fine_similarity, %s student" % student, "pairs": len(cands), "batches": len(parts), "regions": args.regions,
+           "fdim": args.fdim, "stage_reps": args.stage_reps, "g_bit_products" if binary else "g_products": round(flops / 2e9, 2),
+           "slabs_equal_bitwise": same_slabs}
     for name, loc in locs.items():
         out[name] = {"wall": stat(wall[name]), "device": stat(dev[name]), "fine_bytes": loc.fine_bytes,
                      "tera_products_per_s_device_median": round(flops / 2 / (statistics.median(dev[name]) * 1e-3) / 1e12, 2)}
-    out["device_time_ratio_fp32_over_bits"] = round(out["bin_fp32"]["device"]["median_ms"] / out["bits"]["device"]["median_ms"], 2)
-    out["fine_bytes_ratio_fp32_over_bits"] = round(out["bin_fp32"]["fine_bytes"] / out["bits"]["fine_bytes"], 2)
+    tag = "bits" if binary else "f16"
+    out["device_time_ratio_fp32_over_" + tag] = round(out[plain]["device"]["median_ms"] / out[coded]["device"]["median_ms"], 2)
+    out["fine_bytes_ratio_fp32_over_" + tag] = round(out[plain]["fine_bytes"] / out[coded]["fine_bytes"], 2)
+    if not binary:  # the half store buys bytes, not time: its median must stay within the fp32 store's own spread
+        spread = (max(dev[plain]) - min(dev[plain])) / statistics.median(dev[plain])
+        out["fp32_device_spread"] = round(spread, 4)
+        out["fine_bytes_exactly_half"] = out[coded]["fine_bytes"] * 2 == out[plain]["fine_bytes"]
+        out["f16_not_slower"] = statistics.median(dev[coded]) <= statistics.median(dev[plain]) * (1.0 + spread)
     print(json.dumps(out), flush=True)
 
     def batches(loc):
@@ -153,10 +173,10 @@ def fine_codec_leg(np, torch, args, kw):
     res, found = {}, {}
     for name, loc in locs.items():
         res[name], found[name] = timed(torch, lambda: batches(loc), args.steps, args.warmup)
-    same = len(found["bits"]) == len(found["bin_fp32"]) and all(
+    same = len(found[coded]) == len(found[plain]) and all(
         a._replace(score=0.0) == b._replace(score=0.0) and np.float32(a.score).view(np.uint32) == np.float32(b.score).view(np.uint32)
-        for a, b in zip(found["bits"], found["bin_fp32"]))
-    print(json.dumps({"route": "device/chamfer, binary student, both stages", "matches": len(found["bits"]),
+        for a, b in zip(found[coded], found[plain]))
+    print(json.dumps({"route": "device/chamfer, %s student, both stages" % student, "matches": len(found[coded]),
                       "matches_equal_bitwise": same, **{name: res[name] for name in locs}, "box": box()}), flush=True)
 
 
@@ -169,7 +189,7 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--host-steps", type=int, default=2)
-    ap.add_argument("--fine_codec", choices=["bits"], default=None)
+    ap.add_argument("--fine_codec", choices=["bits", "SQfp16"], default=None)
     ap.add_argument("--stage-reps", type=int, default=10)
     ap.add_argument("--skip-routes", action="store_true")
     args = ap.parse_args()

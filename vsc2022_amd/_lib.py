@@ -46,6 +46,7 @@ AGG_TOPMEAN = 3
 FINE_ATT = 0  # VSC_FINE_*: kinds of fine descriptors (vsc_tn_set_fine)
 FINE_BIN = 1
 FINE_BITS = 2  # the 1-bit store of BIN descriptors (vsc_tn_set_fine_bits): a context state, not a kind of vsc_tn_set_fine
+FINE_F16 = 3  # the half-float store of ATT descriptors (vsc_tn_set_fine_f16): a context state as well
 FINE_MAX_REGIONS = 16
 ALIGN_MAX_CELLS = 9216  # VSC_ALIGN_MAX_CELLS: lq * lr of the largest pair whose working state fits LDS
 
@@ -59,7 +60,7 @@ EXPORTS = (
     "vsc_score_histogram", "vsc_score_pick", "vsc_filter_hits", "vsc_argsort_scores", "vsc_merge_topk",
     "vsc_tn_create", "vsc_tn_create_codec", "vsc_tn_ref_bytes", "vsc_tn_set_queries", "vsc_tn_destroy", "vsc_tn_localize", "vsc_tn_forward_sim", "vsc_tn_similarity",
     "vsc_tn_align", "vsc_align_forward_sim", "vsc_tn_set_timestamps", "vsc_tn_match_rows", "vsc_match_metric",
-    "vsc_tn_set_fine", "vsc_tn_set_fine_bits", "vsc_tn_fine_bytes", "vsc_tn_fine_similarity", "vsc_tn_localize_fine", "vsc_tn_similarity_fine",
+    "vsc_tn_set_fine", "vsc_tn_set_fine_bits", "vsc_tn_set_fine_f16", "vsc_tn_fine_bytes", "vsc_tn_fine_similarity", "vsc_tn_localize_fine", "vsc_tn_similarity_fine",
     "vsc_index_profile", "vsc_index_profile_read", "vsc_index_profile_read_class", "vsc_index_search_stats",
     "vsc_aux_profile", "vsc_aux_profile_read", "vsc_bias_act_bf16", "vsc_gemm_bias_act_bf16", "vsc_pool3x3s2_bias_relu_bf16", "vsc_conv_bias_act_bf16",
     "vsc_vit_attention_bf16", "vsc_layernorm_bf16", "vsc_vit_tokens_bf16", "vsc_vit_cdpool_bf16",
@@ -225,6 +226,7 @@ def lib():
         L.vsc_tn_match_rows.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp, i64, i32, pi64]
         L.vsc_tn_set_fine.argtypes = [vp, vp, vp, i32, i32, i32, i32]
         L.vsc_tn_set_fine_bits.argtypes = [vp, vp, vp, i32, i32, i32, i32]
+        L.vsc_tn_set_fine_f16.argtypes = [vp, vp, vp, i32, i32, i32, i32]
         L.vsc_tn_fine_bytes.argtypes = [vp]
         L.vsc_tn_fine_bytes.restype = i64
         L.vsc_tn_fine_similarity.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, i64, i32]

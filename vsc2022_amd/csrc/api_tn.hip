@@ -1,7 +1,7 @@
 // C ABI of libvscmi.so, part 5: the Temporal-Network localisation contexts (vsc_tn_*), the DTW / DP aligners on them
 // (vsc_tn_align), the handle-less forms of both over caller matrices (vsc_tn_forward_sim, vsc_align_forward_sim), the
 // match-rows stage behind them (vsc_tn_set_timestamps, vsc_tn_match_rows) and the DnS fine descriptors (vsc_tn_set_fine,
-// vsc_tn_set_fine_bits, vsc_tn_fine_similarity, vsc_tn_localize_fine, vsc_tn_similarity_fine).  Host plumbing only: the
+// vsc_tn_set_fine_bits, vsc_tn_set_fine_f16, vsc_tn_fine_similarity, vsc_tn_localize_fine, vsc_tn_similarity_fine).  Host plumbing only: the
 // kernels are in tn.hip, align.hip, match_rows.hip, fine_sim.hip and fine_bits.hip.
 #include "api_internal.h"
 
@@ -252,7 +252,8 @@ struct vsc_tn_ctx {
     bool has_qts = false, has_rts = false;
     // DnS fine descriptors (vsc_tn_set_fine): fine_regions packed fp32 rows of fine_dpad floats per frame of either side
     // (bin: +-1) -- or, fine_kind == VSC_FINE_BITS (vsc_tn_set_fine_bits), bit rows of fine_w16 16-byte words in the same
-    // buffers --, the scratch of vsc_tn_fine_similarity (work list, offsets, error word, dense output for host callers)
+    // buffers, or, fine_kind == VSC_FINE_F16 (vsc_tn_set_fine_f16), rows of fine_dpad half floats in natural k order --,
+    // the scratch of vsc_tn_fine_similarity (work list, offsets, error word, dense output for host callers)
     // and of vsc_tn_localize_fine / vsc_tn_similarity_fine (the fine slab of host callers, its offsets, frame counts)
     int fine_regions = 0, fine_dim = 0, fine_dpad = 0, fine_w16 = 0, fine_kind = -1;
     bool has_qfine = false, has_rfine = false;
@@ -324,36 +325,46 @@ static int tn_pack_f16_rows(vsc_tn_ctx* c, const uint16_t* x, int64_t n, int mem
     });
 }
 
-// SQfp16 context: the reference store from fp32 or fp16 rows, by the index codec's encoder (codec_f16.hip: round to
-// nearest even, subnormals kept, natural layout).  All r_rows rows are written, those from n on as zeros.  Host sources
-// are staged in chunks of their own element size: no fp32 image of the rows exists at any time.  The encoder's per-row
-// norm bounds are of no use here and go to a scratch buffer of one chunk.
-static int tn_store_rows(vsc_tn_ctx* c, const void* x, bool src16, int64_t n, int mem, int64_t r_rows) {
+// Half-float rows at `image` ([r_rows][dpad] halves) from `n` fp32 or fp16 rows of `dim` elements, by the index codec's
+// encoder (codec_f16.hip: round to nearest even, subnormals kept, natural layout): the reference store of an SQfp16
+// context (tn_store_rows) and a side of a VSC_FINE_F16 fine store (vsc_tn_set_fine_f16).  All r_rows rows are written,
+// those from n on as zeros.  Host sources are staged in chunks of their own element size: no fp32 image of the rows
+// exists at any time.  The encoder's per-row norm bounds are of no use here and go to a scratch buffer of one chunk
+// (ws.qn).  *refused: an element was NaN, +-inf or beyond +-65504 -- the caller names it and drops what was written.
+static int tn_encode_rows(vsc_tn_ctx* c, const void* x, bool src16, int64_t n, int dim, int dpad, int mem, _Float16* image,
+                          int64_t r_rows, bool* refused) {
     const size_t esz = src16 ? 2 : 4;
     Workspace& ws = c->ws;
+    *refused = false;
     VSC_TRY(ws.flag.reserve(16));
     int* d_bad = ws.flag.as<int>();
     VSC_HIP(hipMemsetAsync(d_bad, 0, sizeof(int), c->stream));
-    _Float16* image = c->rfeat_h.as<_Float16>();
-    const int64_t chunk_rows = std::max<int64_t>(ROW_PAD, (int64_t)(256ll << 20) / ((int64_t)c->dim * (int64_t)esz));
+    const int64_t chunk_rows = std::max<int64_t>(ROW_PAD, (int64_t)(256ll << 20) / ((int64_t)dim * (int64_t)esz));
     VSC_TRY(ws.qn.reserve((size_t)std::min(chunk_rows, r_rows) * 4));
     const bool host = mem != VSC_MEM_DEVICE;
-    if (host && n > 0) VSC_TRY(ws.stage.reserve((size_t)std::min(chunk_rows, n) * c->dim * esz));
+    if (host && n > 0) VSC_TRY(ws.stage.reserve((size_t)std::min(chunk_rows, n) * dim * esz));
     for (int64_t r0 = 0; r0 < r_rows; r0 += chunk_rows) {
         const int64_t rows_out = std::min(chunk_rows, r_rows - r0);
         const int64_t rows = std::max<int64_t>(0, std::min(rows_out, n - r0));  // source rows of the chunk
-        const void* src = rows ? static_cast<const char*>(x) + (size_t)r0 * c->dim * esz : nullptr;
+        const void* src = rows ? static_cast<const char*>(x) + (size_t)r0 * dim * esz : nullptr;
         if (host && rows) {
-            VSC_HIP(hipMemcpyAsync(ws.stage.p, src, (size_t)rows * c->dim * esz, hipMemcpyHostToDevice, c->stream));
+            VSC_HIP(hipMemcpyAsync(ws.stage.p, src, (size_t)rows * dim * esz, hipMemcpyHostToDevice, c->stream));
             src = ws.stage.p;
         }
-        VSC_TRY(launch_encode_rows(src, src16, rows, c->dim, image, ws.qn.as<float>(), r0, rows_out, c->dpad, false, d_bad, c->stream));
+        VSC_TRY(launch_encode_rows(src, src16, rows, dim, image, ws.qn.as<float>(), r0, rows_out, dpad, false, d_bad, c->stream));
         if (host) VSC_HIP(hipStreamSynchronize(c->stream));  // the staging buffer is reused
     }
     int bad = 0;
     VSC_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     VSC_HIP(hipStreamSynchronize(c->stream));
-    if (bad) {
+    *refused = bad != 0;
+    return VSC_OK;
+}
+
+static int tn_store_rows(vsc_tn_ctx* c, const void* x, bool src16, int64_t n, int mem, int64_t r_rows) {
+    bool refused = false;
+    VSC_TRY(tn_encode_rows(c, x, src16, n, c->dim, c->dpad, mem, c->rfeat_h.as<_Float16>(), r_rows, &refused));
+    if (refused) {
         set_error("vsc_tn_create_codec: a reference row holds NaN, +-inf or a value beyond +-65504, which the SQfp16 codec cannot store");
         return VSC_ERR_INVALID;
     }
@@ -990,6 +1001,47 @@ int vsc_tn_set_fine_bits(vsc_tn_ctx_t* c, const void* qfine, const void* rfine, 
     return VSC_OK;
 }
 
+int vsc_tn_set_fine_f16(vsc_tn_ctx_t* c, const void* qfine, const void* rfine, int regions, int fdim, int src_f16, int mem) {
+    if (!c || regions < 1 || regions > VSC_FINE_MAX_REGIONS || fdim < 1 || (src_f16 != 0 && src_f16 != 1)) {
+        set_error("vsc_tn_set_fine_f16: invalid argument (regions 1..%d, fdim >= 1, src_f16 0 / 1)", VSC_FINE_MAX_REGIONS);
+        return VSC_ERR_INVALID;
+    }
+    VSC_HIP(hipSetDevice(c->device));
+    if (regions != c->fine_regions || fdim != c->fine_dim || c->fine_kind != VSC_FINE_F16) {
+        // (as vsc_tn_set_fine: a side kept from another shape or kind could not meet the new one)
+        c->has_qfine = c->has_rfine = false;
+        c->qfine_bytes = c->rfine_bytes = 0;
+    }
+    c->fine_regions = regions;
+    c->fine_dim = fdim;
+    c->fine_kind = VSC_FINE_F16;
+    c->fine_dpad = round_up(fdim, K_PAD);  // (halves per row: a multiple of 128 bytes, every 16-byte piece aligned)
+    struct Side { const void* x; int64_t frames; DevBuf* buf; bool* has; int64_t* bytes; const char* name; };
+    Side sides[2] = {{qfine, c->q_off.back(), &c->qfine, &c->has_qfine, &c->qfine_bytes, "query"},
+                     {rfine, c->r_off.back(), &c->rfine, &c->has_rfine, &c->rfine_bytes, "reference"}};
+    for (Side& s : sides) {
+        if (!s.x) continue;
+        *s.has = false;  // (until the new rows are down; for good if an element is refused: no half-written side is read)
+        *s.bytes = 0;
+        const int64_t rows = s.frames * regions;
+        // +64 rows of slack, zeroed: the 64-row tiles of the last video's last frames read past its end (fine_sim.hip)
+        const int64_t rows_out = round_up64(rows + 64, ROW_PAD);
+        VSC_TRY(s.buf->reserve((size_t)rows_out * c->fine_dpad * 2));
+        bool refused = false;
+        VSC_TRY(tn_encode_rows(c, s.x, src_f16 != 0, rows, fdim, c->fine_dpad, mem, s.buf->as<_Float16>(), rows_out, &refused));
+        c->ws.qn.release();  // (scratch of the encoder)
+        if (refused) {
+            set_error("vsc_tn_set_fine_f16: a %s fine descriptor holds NaN, +-inf or a value beyond +-65504, which a half float "
+                      "cannot store (the context keeps no %s fine descriptors)", s.name, s.name);
+            return VSC_ERR_INVALID;
+        }
+        *s.bytes = rows_out * c->fine_dpad * 2;
+        *s.has = true;
+    }
+    VSC_HIP(hipStreamSynchronize(c->stream));
+    return VSC_OK;
+}
+
 int64_t vsc_tn_fine_bytes(const vsc_tn_ctx_t* c) { return c ? c->qfine_bytes + c->rfine_bytes : 0; }
 
 int vsc_tn_fine_similarity(vsc_tn_ctx_t* c, const int32_t* pair_q, const int32_t* pair_r, int64_t n_pairs, int pairs_mem,
@@ -1093,9 +1145,11 @@ int vsc_tn_fine_similarity(vsc_tn_ctx_t* c, const int32_t* pair_q, const int32_t
         bind(a);
         a.qfine = c->qfine.as<float>();
         a.rfine = c->rfine.as<float>();
+        a.qfine_h = c->qfine.as<_Float16>();  // (the same buffers: the store's kind says which of the two is read)
+        a.rfine_h = c->rfine.as<_Float16>();
         a.dpad = c->fine_dpad;
         a.bin = c->fine_kind == VSC_FINE_BIN;
-        VSC_TRY(launch_fine_sim(a, c->stream));
+        VSC_TRY(launch_fine_sim(a, c->stream, c->fine_kind == VSC_FINE_F16));
     }
     int err = 0;
     VSC_HIP(hipMemcpyAsync(&err, c->d_ferr.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));

@@ -21,6 +21,10 @@
 // similarity kernel reaches 137 TFLOP/s).  Every tile re-reads its rows from L2 (no operand staging in LDS) and a
 // quarter of the lanes idle in the reductions at R = 16.  Measured at that shape (profiles/dns_device.md): 58 TFLOP/s.
 //
+// VSC_FINE_F16 (the attention student's descriptors as the half floats its indexer writes) is this kernel with the rows
+// of both operands read as halves (FineRows<true>): half the bytes from L2, the same chain, the bits of the fp32 store
+// of the decoded values.  Measured: profiles/fine_f16.md.
+//
 // VSC_FINE_BIN rows are +-1 fp32 here (the chain's result divided once by the width).  The 1-bit store of the same
 // descriptors (VSC_FINE_BITS) has its own step 1 in fine_bits.hip -- xor + popcount, the same bits -- and shares steps
 // 2-4 with this kernel through fine_chamfer.h (FS_TILE = 64 region rows / columns per work item: 2 x 2 MFMA blocks here).
@@ -32,6 +36,25 @@ namespace vscmi {
 
 int fine_sim_frames(int regions) { return FS_TILE / regions; }
 
+// Where step 1 reads its operand rows from (template parameter H16 of fine_sim_kernel), as TnRef of tn_sims.h:
+//   false: the packed fp32 rows -- the 16-byte load at float offset hi * 4 of k-group g hands lane half `hi` its
+//          k = 8 g + 2 s + hi, s = 0..3.
+//   true:  the half-float rows of a VSC_FINE_F16 context on BOTH operands (natural k order): both lane halves load the
+//          whole 16-byte piece g and keep their even or odd elements, converted by the hardware cvt (exact) --
+//          tn_ref_piece.  The same values in the same order enter the chain as from the packed fp32 image of dec(X).
+template <bool H16> struct FineRows;
+template <> struct FineRows<false> {
+    typedef float T;
+    static __device__ __forceinline__ const T* q(const FineSimArgs& a, int64_t row, int hi) { return a.qfine + row * a.dpad + hi * 4; }
+    static __device__ __forceinline__ const T* r(const FineSimArgs& a, int64_t row, int hi) { return a.rfine + row * a.dpad + hi * 4; }
+};
+template <> struct FineRows<true> {
+    typedef _Float16 T;
+    static __device__ __forceinline__ const T* q(const FineSimArgs& a, int64_t row, int) { return a.qfine_h + row * a.dpad; }
+    static __device__ __forceinline__ const T* r(const FineSimArgs& a, int64_t row, int) { return a.rfine_h + row * a.dpad; }
+};
+
+template <bool H16>
 __global__ __launch_bounds__(256) void fine_sim_kernel(FineSimArgs a) {
     __shared__ float G[FS_TILE * FS_LD];
     __shared__ float fwd[FS_TILE * FS_TILE];  // [frame pair][a]: max over b
@@ -53,16 +76,16 @@ __global__ __launch_bounds__(256) void fine_sim_kernel(FineSimArgs a) {
     // ---- 1. the 64 x 64 piece of G: one 32 x 32 block per wavefront, K ascending; blocks of padding only are skipped ----
     const int qb = (wave >> 1) * 32, rb = (wave & 1) * 32;
     if (qb < nfq * R && rb < nfr * R) {
-        const float* ap = a.qfine + ((q0 + qf0) * R + qb + l31) * a.dpad + hi * 4;
-        const float* bp = a.rfine + ((r0 + rf0) * R + rb + l31) * a.dpad + hi * 4;
+        const typename FineRows<H16>::T* ap = FineRows<H16>::q(a, (q0 + qf0) * R + qb + l31, hi);
+        const typename FineRows<H16>::T* bp = FineRows<H16>::r(a, (r0 + rf0) * R + rb + l31, hi);
         f32x16 acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
         const int nkg = a.dpad / 8;
 #pragma unroll 4
         for (int g = 0; g < nkg; ++g) {
-            const f32x4 av = *reinterpret_cast<const f32x4*>(ap + g * 8);
-            const f32x4 bv = *reinterpret_cast<const f32x4*>(bp + g * 8);
+            const f32x4 av = tn_ref_piece(ap, g, hi);
+            const f32x4 bv = tn_ref_piece(bp, g, hi);
 #pragma unroll
             for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], bv[s], acc, 0, 0, 0);
         }
@@ -79,9 +102,10 @@ __global__ __launch_bounds__(256) void fine_sim_kernel(FineSimArgs a) {
     fine_chamfer_reduce(G, fwd, bwd, tid, R, nfq, nfr, a.symmetric, a.out, a.out_off, p, lr, qf0, rf0);
 }
 
-int launch_fine_sim(const FineSimArgs& a, hipStream_t stream) {
+int launch_fine_sim(const FineSimArgs& a, hipStream_t stream, bool half_rows) {
     if (a.n_work <= 0) return VSC_OK;
-    hipLaunchKernelGGL(fine_sim_kernel, dim3((unsigned)a.n_work), dim3(256), 0, stream, a);
+    if (half_rows) hipLaunchKernelGGL(fine_sim_kernel<true>, dim3((unsigned)a.n_work), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(fine_sim_kernel<false>, dim3((unsigned)a.n_work), dim3(256), 0, stream, a);
     VSC_HIP(hipGetLastError());
     return VSC_OK;
 }

@@ -197,6 +197,10 @@ struct FineSimArgs {
     int regions, fdim, dpad, bin, symmetric;
     float* out; const int64_t* out_off;  // F of pair p, row-major lq x lr, at out + out_off[p]
     int* err;  // error word: bit 0 = a pair ordinal outside the context's videos (that work item is skipped)
+    // VSC_FINE_F16 (launch_fine_sim's `half_rows`): the rows of both sides as half floats instead -- [rows][dpad] halves,
+    // natural k order, zero padded, as launch_encode_rows(..., frag = false) writes them; qfine / rfine are not read.
+    // (Last, so that the fp32 kernel finds every other field where it was.)
+    const _Float16* qfine_h; const _Float16* rfine_h;
 };
 // The same on the 1-bit store (fine_bits.hip, VSC_FINE_BITS): FineSimArgs' fields under FineSimArgs' names, the rows as bits
 struct FineBitsArgs {
@@ -360,7 +364,7 @@ size_t tn_state_bytes_host(int, int, int, int idx_bytes = 2);
 int launch_tn_pairs(const TnPairArgs&, size_t, hipStream_t);
 int launch_tn_sims(const TnSimsArgs&, hipStream_t);
 int fine_sim_frames(int regions);  // frames per side of a work item of launch_fine_sim
-int launch_fine_sim(const FineSimArgs&, hipStream_t);
+int launch_fine_sim(const FineSimArgs&, hipStream_t, bool half_rows = false);
 int launch_bin_to_pm1(const uint8_t*, int64_t, float*, hipStream_t);
 int fine_bits_row_words(int fdim);  // 16-byte words of one bit row (fine_bits.hip)
 int launch_fine_bits(const FineBitsArgs&, hipStream_t);

@@ -31,6 +31,13 @@ localisation on the device"): with a torch model both routes see the same F bits
 HBM as the bits they are, 1/32 of the default +-1 fp32 rows: each video is packed on the host
 (`pack_fine_bits`), `vsc_tn_set_fine_bits` stores the rows and stage 1 runs on xor + popcount (fine_bits.hip).  The
 results are the bits of the default store: include/vscmi.h writes down why.
+
+`fine_codec="SQfp16"` (with on_device=True and `ChamferSimilarity` WITHOUT "bin" only) keeps the attention student's
+descriptors in HBM as half floats -- what dns_index writes for it (`feature.half()`) -- at half the bytes of the default
+fp32 rows.  float16 features go down as they are (`vsc_tn_set_fine_f16`, no fp32 copy on the host, half the transfer)
+and give the default store's results bit for bit; other dtypes are rounded to half by the library (round to nearest
+even), and the results are those of the default store on the rounded values.  A value a half cannot hold (NaN, inf,
+beyond +-65504) is a ValueError.
 """
 import argparse
 import ctypes
@@ -62,7 +69,7 @@ def _by_id(features: FineFeatures) -> Dict[object, VideoFeature]:
     return {v.video_id: v for v in features}
 
 
-FINE_CODECS = ("bits",)
+FINE_CODECS = ("bits", "SQfp16")
 
 
 def pack_fine_bits(feature) -> np.ndarray:
@@ -79,7 +86,16 @@ def _check_fine_codec(fine_codec, on_device: bool, model):
         raise ValueError(f"unknown fine_codec {fine_codec!r} (None or one of {FINE_CODECS})")
     if not on_device:
         raise ValueError(f"fine_codec={fine_codec!r} is a store of the device route: it needs on_device=True")
-    if type(model) is not ChamferSimilarity or "bin" not in getattr(model, "fg_type", ""):
+    binary = "bin" in getattr(model, "fg_type", "")
+    if fine_codec == "SQfp16":
+        if type(model) is not ChamferSimilarity:
+            raise ValueError(f"fine_codec={fine_codec!r} keeps half-float descriptors for libvscmi's region Chamfer kernel: the "
+                             "model must be exactly ChamferSimilarity (a torch model holds its own tensors)")
+        if binary:
+            raise ValueError(f"fine_codec={fine_codec!r} is the store of an attention student's descriptors: for a binary "
+                             "student (\"bin\" in fg_type) the store to use is fine_codec=\"bits\"")
+        return
+    if type(model) is not ChamferSimilarity or not binary:
         raise ValueError(f"fine_codec={fine_codec!r} packs binary descriptors for libvscmi's region Chamfer kernel: the model "
                          "must be exactly ChamferSimilarity with \"bin\" in fg_type")
 
@@ -139,9 +155,11 @@ class VCSLLocalizationDnS(VCSLLocalizationMaxSim):
     def _upload_fine(self):
         """The fine descriptors of both sides, in the order of the context's videos, down once (vsc_tn_set_fine; with
         fine_codec="bits" packed video by video first, so that the host staging copy is D / 8 bytes per region, and
-        handed to vsc_tn_set_fine_bits)."""
+        handed to vsc_tn_set_fine_bits; with fine_codec="SQfp16" handed to vsc_tn_set_fine_f16, as the halves they are
+        when every video's descriptors are float16 -- no fp32 copy exists on the host -- and as fp32 otherwise)."""
         binary = "bin" in self.sim_model.fg_type
         bits = self.fine_codec == "bits"
+        half = self.fine_codec == "SQfp16"
         sides = []
         for videos, table in ((self._q_videos, self.queries_fine), (self._r_videos, self.refs_fine)):
             parts = []
@@ -157,11 +175,16 @@ class VCSLLocalizationDnS(VCSLLocalizationMaxSim):
         if not shapes:
             return
         regions, width = shapes.pop()
-        rows = [np.ascontiguousarray(np.concatenate([x for _, x in parts], axis=0), dtype=np.uint8 if binary else np.float32)
-                if parts else None for parts in sides]
+        dtype = np.uint8 if binary else np.float32
+        if half and all(x.dtype == np.float16 for parts in sides for _, x in parts):
+            dtype = np.float16
+        rows = [np.ascontiguousarray(np.concatenate([x for _, x in parts], axis=0), dtype=dtype) if parts else None for parts in sides]
         addr = [x.ctypes.data if x is not None and x.size else None for x in rows]
         if bits:
             _lib.check(_lib.lib().vsc_tn_set_fine_bits(self._ctx, addr[0], addr[1], int(regions), int(width), 1, _lib.MEM_HOST))
+        elif half:
+            _lib.check(_lib.lib().vsc_tn_set_fine_f16(self._ctx, addr[0], addr[1], int(regions), int(width),
+                                                      int(dtype == np.float16), _lib.MEM_HOST))
         else:
             _lib.check(_lib.lib().vsc_tn_set_fine(self._ctx, addr[0], addr[1], int(regions), int(width),
                                                   _lib.FINE_BIN if binary else _lib.FINE_ATT, _lib.MEM_HOST))
@@ -311,7 +334,8 @@ def localize_and_verify(model, queries_fine: FineFeatures, refs_fine: FineFeatur
                         refs_coarse: List[VideoFeature], candidates: Sequence[CandidatePair],
                         localize_per_query: float = 5.0, device="cpu", on_device: bool = False, fine_codec=None) -> List[Match]:
     """Reference :183-227: the best `localize_per_query * len(queries_fine)` candidates, batches of 512 pairs.
-    on_device: `VCSLLocalizationDnS(on_device=True)`, every matrix stays in HBM; fine_codec: its store of the fine rows."""
+    on_device: `VCSLLocalizationDnS(on_device=True)`, every matrix stays in HBM; fine_codec: its store of the fine rows
+    (one of FINE_CODECS)."""
     todo = candidates[: int(len(queries_fine) * localize_per_query)]
     aligner = VCSLLocalizationDnS(model, queries_fine, refs_fine, queries_coarse, refs_coarse, model_type="TN",
                                   tn_max_step=5, min_length=4, concurrency=16, similarity_bias=0.5, device=device,
@@ -355,7 +379,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--on_device", help="Keep the similarity matrices of the localisation in HBM (needs a GPU accelerator).",
                    action="store_true")
     p.add_argument("--fine_codec", help="Store of the fine descriptors in HBM with --on_device: bits = 1 bit per value "
-                   "(binary students through ChamferSimilarity only).", choices=list(FINE_CODECS), default=None)
+                   "(binary students through ChamferSimilarity only), SQfp16 = half floats (attention students through "
+                   "ChamferSimilarity only).", choices=list(FINE_CODECS), default=None)
     return p
 
 
