@@ -722,6 +722,25 @@ int vsc_vit_tokens_bf16(const void* patch, const float* cls, const float* pos, v
 int vsc_vit_cdpool_bf16(const void* x, const float* gamma, const float* beta, float* out, int64_t B, int64_t N,
                         int64_t C, float eps, void* hip_stream);
 
+/* ------------------------------------------------- DnS L3-iMAC region descriptors (--baseline dns --fast)
+ * Region max-pool of an NHWC bf16 activation with the channel L2 normalisation in the same kernel: x [B, H, W, C] bf16
+ * (a stage output of the trunk as it stands in memory), grid gh = (H - win) / stride + 1, gw likewise (no padding,
+ * floor); m[c] = max over dy, dx < win of x[b, gy * stride + dy, gx * stride + dx, c], over signed values (bf16 widens
+ * to fp32 exactly, so the maximum is exact), and
+ *     out[(b * gh * gw + gy * gw + gx) * out_row + out_col + c] = m[c] / max(sqrt(sum_c m[c]^2), eps)
+ * with the sum (in no fixed order), root and division in fp32.  out is fp32 with rows of out_row floats; columns outside
+ * [out_col, out_col + C) of a row are not written, so the taps of a network fill column slices of one buffer.
+ * C a multiple of 8 and <= 4096; win, stride >= 1; H, W >= win; out_row >= out_col + C; eps >= 0; x 16-byte aligned;
+ * anything else, or a NULL pointer with B > 0, is VSC_ERR_INVALID before any device call.  B = 0 is a no-op.  Inputs
+ * must be finite and zero or of magnitude within [2^-50, 2^50] (not checked): the squares and their sum then stay
+ * inside fp32's normal range.  Device pointers only; same stream convention as the kernels above. */
+int vsc_region_pool_l2_bf16(const void* x, float* out, int64_t B, int64_t H, int64_t W, int64_t C, int win, int stride,
+                            int64_t out_row, int64_t out_col, float eps, void* hip_stream);
+/* In place x[r, :] /= max(||x[r, :]||_2, eps) on an fp32 device matrix [rows, cols]: torch's F.normalize, which clamps
+ * the norm from below -- not sklearn's normalisation, which leaves zero rows alone and is what the host-or-device
+ * row normaliser of the search API implements.  rows >= 0 (0: no-op), cols >= 1, eps >= 0. */
+int vsc_rows_l2norm_f32(float* x, int64_t rows, int64_t cols, float eps, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -64,6 +64,7 @@ EXPORTS = (
     "vsc_index_profile", "vsc_index_profile_read", "vsc_index_profile_read_class", "vsc_index_search_stats",
     "vsc_aux_profile", "vsc_aux_profile_read", "vsc_bias_act_bf16", "vsc_gemm_bias_act_bf16", "vsc_pool3x3s2_bias_relu_bf16", "vsc_conv_bias_act_bf16",
     "vsc_vit_attention_bf16", "vsc_layernorm_bf16", "vsc_vit_tokens_bf16", "vsc_vit_cdpool_bf16",
+    "vsc_region_pool_l2_bf16", "vsc_rows_l2norm_f32",
 )
 
 
@@ -249,6 +250,8 @@ def lib():
         L.vsc_layernorm_bf16.argtypes = [vp, vp, vp, vp, i64, i64, f32, vp]
         L.vsc_vit_tokens_bf16.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp]
         L.vsc_vit_cdpool_bf16.argtypes = [vp, vp, vp, vp, i64, i64, i64, f32, vp]
+        L.vsc_region_pool_l2_bf16.argtypes = [vp, vp, i64, i64, i64, i64, i32, i32, i64, i64, f32, vp]
+        L.vsc_rows_l2norm_f32.argtypes = [vp, i64, i64, f32, vp]
         for name in EXPORTS:
             fn = getattr(L, name)
             if fn.restype is ctypes.c_int and name not in ("vsc_version", "vsc_device_count"):

@@ -56,19 +56,28 @@ class Bottleneck(nn.Module):
         return F.relu(x + idt, inplace=True)
 
 
+RESNET50_STAGES = ((64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 2))  # (planes, blocks, stride of the first block)
+
+
+def resnet50_stem_trunk() -> Tuple[nn.Sequential, nn.Sequential]:
+    """torchvision's resnet50 without avgpool / fc, tensors in its order: the stem (conv 7x7 / 2, BN, ReLU, max-pool
+    3x3 / 2) and the 3 + 4 + 6 + 3 bottlenecks as one Sequential."""
+    stem = nn.Sequential(nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False), nn.BatchNorm2d(64),
+                         nn.ReLU(inplace=True), nn.MaxPool2d(3, stride=2, padding=1))
+    layers, inplanes = [], 64
+    for planes, blocks, stride in RESNET50_STAGES:
+        for b in range(blocks):
+            layers.append(Bottleneck(inplanes, planes, stride if b == 0 else 1))
+            inplanes = planes * 4
+    return stem, nn.Sequential(*layers)
+
+
 class SSCDModel(nn.Module):
     """ResNet-50 trunk -> GeM(p=3) -> Linear(2048 -> dims); no final L2 normalisation."""
 
     def __init__(self, dims: int = 512, gem_p: float = 3.0):
         super().__init__()
-        self.stem = nn.Sequential(nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False), nn.BatchNorm2d(64),
-                                  nn.ReLU(inplace=True), nn.MaxPool2d(3, stride=2, padding=1))
-        layers, inplanes = [], 64
-        for planes, blocks, stride in ((64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 2)):
-            for b in range(blocks):
-                layers.append(Bottleneck(inplanes, planes, stride if b == 0 else 1))
-                inplanes = planes * 4
-        self.trunk = nn.Sequential(*layers)
+        self.stem, self.trunk = resnet50_stem_trunk()
         self.gem_p = gem_p
         self.embed = nn.Linear(2048, dims)
 
@@ -289,23 +298,18 @@ class FastBottleneck(nn.Module):
         return out.view(n2, h2, w2, -1).permute(0, 3, 1, 2)
 
 
-class FastSSCD(nn.Module):
-    """`SSCDModel` prepared for inference on the GPU: BatchNorms folded, stem and trunk in bf16 (NHWC), blocks as
-    `FastBottleneck`; GeM and the embedding stay in fp32.  Takes the fp32 frames `preprocess` returns.  The accuracy
-    gate against the fp32 eager network is tests/test_inference.py::test_fast_inference_configuration_against_fp32_eager."""
+class FastTrunk(nn.Module):
+    """The ResNet-50 stem and trunk of a BatchNorm-folded network (`fold_batchnorm`: `.stem`, `.trunk`) prepared for
+    inference on the GPU: bf16 NHWC, blocks as `FastBottleneck`.  What `FastSSCD` and `inference_l3imac.FastL3iMAC`
+    share; a subclass adds its head in `_forward`."""
 
-    def __init__(self, model: "SSCDModel"):
+    def __init__(self, folded: nn.Module):
         super().__init__()
-        m = fold_batchnorm(model)
-        self.stem_conv = m.stem[0].to(torch.bfloat16).to(memory_format=torch.channels_last)
+        self.stem_conv = folded.stem[0].to(torch.bfloat16).to(memory_format=torch.channels_last)
         self.stem_bias = nn.Parameter(self.stem_conv.bias.detach().float().clone(), requires_grad=False)
         self.stem_conv.bias = None
-        self.pool = m.stem[3]
-        self.blocks = nn.ModuleList(FastBottleneck(b) for b in m.trunk)
-        self.gem_p = m.gem_p
-        self.embed = m.embed
-        for p in self.parameters():
-            p.requires_grad_(False)
+        self.pool = folded.stem[3]
+        self.blocks = nn.ModuleList(FastBottleneck(b) for b in folded.trunk)
 
     def forward(self, x):
         # the hand-written kernels launch on torch's current stream OF THE TENSOR'S DEVICE and never switch devices
@@ -313,14 +317,30 @@ class FastSSCD(nn.Module):
         with torch.cuda.device(x.device):
             return self._forward(x)
 
-    def _forward(self, x):
+    def _stem(self, x):
         x = self.stem_conv(x.to(torch.bfloat16).contiguous(memory_format=torch.channels_last))
         if _FUSED_POOL and x.permute(0, 2, 3, 1).is_contiguous():
-            x = _pool_bias_relu(x, self.stem_bias)                                        # bias + relu + max-pool, one pass
-        else:
-            n, _, h, w = x.shape
-            x = _bias_act(_rows(x), self.stem_bias, None, True).view(n, h, w, -1).permute(0, 3, 1, 2)
-            x = self.pool(x)
+            return _pool_bias_relu(x, self.stem_bias)                                     # bias + relu + max-pool, one pass
+        n, _, h, w = x.shape
+        x = _bias_act(_rows(x), self.stem_bias, None, True).view(n, h, w, -1).permute(0, 3, 1, 2)
+        return self.pool(x)
+
+
+class FastSSCD(FastTrunk):
+    """`SSCDModel` prepared for inference on the GPU: BatchNorms folded, stem and trunk in bf16 (NHWC), blocks as
+    `FastBottleneck`; GeM and the embedding stay in fp32.  Takes the fp32 frames `preprocess` returns.  The accuracy
+    gate against the fp32 eager network is tests/test_inference.py::test_fast_inference_configuration_against_fp32_eager."""
+
+    def __init__(self, model: "SSCDModel"):
+        m = fold_batchnorm(model)
+        super().__init__(m)
+        self.gem_p = m.gem_p
+        self.embed = m.embed
+        for p in self.parameters():
+            p.requires_grad_(False)
+
+    def _forward(self, x):
+        x = self._stem(x)
         for b in self.blocks:
             x = b(x)
         x = x.float().clamp(min=1e-6).pow(self.gem_p).mean(dim=(2, 3)).pow(1.0 / self.gem_p)

@@ -23,11 +23,15 @@ Deliberate differences: (1) `--video_reader NPY` reads `<name>.npy` uint8 stacks
 like the reference's `video_reader/ffmpeg_video_reader.py:29-56` and fails loudly when the binary is missing;
 (2) without `--torchscript_path` a random-init network is used (benchmarks only: there are no weights to download
 here) and the run says so: the SSCD architecture, or with `--baseline dino` DINO's ViT-S/16 + copy-detection pool
-(`inference_vit.build_dino_model`); `--baseline dns` needs a TorchScript file.  As in the reference, `--baseline` does
-not change how a TorchScript file runs.
+(`inference_vit.build_dino_model`); `--baseline dns` needs a TorchScript file (the L3-iMAC extractor of the reference's
+docs/baseline_dns.md: `--baseline dns --torchscript_path resnet50_l3imac.torchscript.pt --transforms RESIZE_224_SQUARE
+--store_fp16 --batch_size 128` writes [frames, 9, 3840] region descriptors per video, the input of `dns_index`).  As in
+the reference, `--baseline` does not change how a TorchScript file runs.
 
-`--fast` (extension) recognises the architecture from the export itself -- a ResNet-50 SSCD trunk (`FastSSCD`) or a
-DINO ViT + cdpool (`inference_vit.FastDINO`) -- and runs it through the library's kernels behind `CheckedFast`.
+`--fast` (extension) recognises the architecture from the export itself -- a ResNet-50 SSCD trunk (`FastSSCD`), a
+DINO ViT + cdpool (`inference_vit.FastDINO`) or the DnS L3-iMAC ResNet-50 (`inference_l3imac.FastL3iMAC`) -- and runs it
+through the library's kernels behind `CheckedFast`, which compares every descriptor (every region vector of every frame
+for L3-iMAC) of the first batch with the fp32 network.
 """
 import argparse
 import enum
@@ -219,7 +223,8 @@ class CheckedFast(torch.nn.Module):
     """`FastSSCD` behind a gate on REAL data: the bf16 configuration is accuracy-tested on a calibrated
     random-init trunk (tests/test_inference.py), which says nothing about a particular checkpoint.  On the first batch
     of frames the fp32 eager network runs as well; if any frame's descriptors agree worse than `min_cosine` the fast
-    network is dropped for the rest of the run (with a warning) and the eager one answers."""
+    network is dropped for the rest of the run (with a warning) and the eager one answers.  The cosine is taken along
+    the last dimension: with [B, R, D] outputs (L3-iMAC) the gate reads every region vector of every frame."""
 
     def __init__(self, fast: torch.nn.Module, eager: torch.nn.Module, min_cosine: float = 0.999):
         super().__init__()
@@ -233,7 +238,8 @@ class CheckedFast(torch.nn.Module):
         if not self.checked:
             self.checked = True
             ref = self.eager(x)
-            cos = torch.nn.functional.cosine_similarity(ref.float(), y.float(), dim=1)
+            # along the descriptor dimension, minimum over everything else: every region vector of every frame
+            cos = torch.nn.functional.cosine_similarity(ref.float(), y.float(), dim=-1)
             self.first_batch_cosine = float(cos.min().item()) if cos.numel() else 1.0
             if not (self.first_batch_cosine >= self.min_cosine):
                 logger.warning(f"--fast: descriptors of the first batch agree with the fp32 network only to cosine "
@@ -265,7 +271,9 @@ def load_model(args, device):
     if getattr(args, "fast", False):
         # (not a reference flag) the same weights through the library's kernels: FastSSCD (bf16 NHWC trunk, GEMM 1x1,
         # fused epilogues) or FastDINO (bf16 ViT: fused GEMM epilogues, attention, LayerNorm, cdpool head)
+        # or FastL3iMAC (the same bf16 trunk, region pooling + channel normalisation of the four taps as one kernel each)
         from vsc2022_amd.vsc.baseline.inference import FastSSCD, SSCDModel, sscd_from_module
+        from vsc2022_amd.vsc.baseline.inference_l3imac import FastL3iMAC, l3imac_from_module
         from vsc2022_amd.vsc.baseline.inference_vit import DinoModel, FastDINO, dino_from_module
 
         if device.type != "cuda":
@@ -276,15 +284,15 @@ def load_model(args, device):
         elif isinstance(model, DinoModel):
             eager, fast = model, FastDINO
         else:
-            eager = sscd_from_module(model)
-            if eager is not None:
-                fast = FastSSCD
-            else:
-                eager = dino_from_module(model)
-                fast = FastDINO if eager is not None else None
+            for recognise, cls in ((sscd_from_module, FastSSCD), (dino_from_module, FastDINO), (l3imac_from_module, FastL3iMAC)):
+                eager = recognise(model)
+                if eager is not None:
+                    fast = cls
+                    break
         if fast is None:
-            raise Exception("--fast: the model is neither a ResNet-50 trunk + GeM + Linear nor a DINO ViT + cdpool (or "
-                            "does not reproduce on a random batch after conversion); run without --fast")
+            raise Exception("--fast: the model is neither a ResNet-50 trunk + GeM + Linear nor a DINO ViT + cdpool nor a "
+                            "DnS L3-iMAC ResNet-50 (or does not reproduce on a random batch after conversion); run "
+                            "without --fast")
         model = CheckedFast(fast(eager).to(device).eval(), eager, getattr(args, "fast_min_cosine", 0.999)).eval()
     return model
 
@@ -321,8 +329,8 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--scratch_path", required=False)
     g.add_argument("--store_fp16", action="store_true")
     g.add_argument("--fast", action="store_true",
-                   help="(extension) run a ResNet-50 SSCD model (FastSSCD) or a DINO ViT + cdpool (FastDINO) through "
-                        "the library's bf16 kernels; cuda only")
+                   help="(extension) run a ResNet-50 SSCD model (FastSSCD), a DINO ViT + cdpool (FastDINO) or a DnS L3-iMAC "
+                        "ResNet-50 (FastL3iMAC) through the library's bf16 kernels; cuda only")
     g.add_argument("--fast_min_cosine", type=float, default=0.999,
                    help="(extension) --fast: the first batch is also run on the fp32 network; below this per-frame "
                         "cosine the run continues on the fp32 network")
