@@ -192,6 +192,85 @@ def test_stage1_arguments(gpu, orc):
         c.close()
 
 
+def test_failed_upload_of_another_shape_keeps_no_side(gpu, orc):
+    """A store of another kind or shape drops both sides before the first upload: when the query side is then refused, the
+    reference side of the old store is gone too, though its own upload was never reached.  (The new rows are no larger
+    than the old ones.)"""
+    from vsc2022_amd import _lib
+
+    rng = np.random.default_rng(9)
+    qc, rc = [ref.unit_rows(rng, n, 16) for n in (5, 9)], [ref.unit_rows(rng, n, 16) for n in (8, 3)]
+    qf, rf = _fine_inputs(3, (5, 9), 4, 16, "att"), _fine_inputs(4, (8, 3), 4, 16, "att")
+    c = Ctx(qc, rc)
+    try:
+        pairs = [(0, 0), (1, 1)]
+        c.set_fine(qf, rf, "att")
+        assert c.fine_similarity(pairs, True)[0] == 0
+        good_q = np.ascontiguousarray(np.concatenate(qf)[:, :, :8])
+        good_r = np.ascontiguousarray(np.concatenate(rf)[:, :, :8])
+        bad_q = good_q.copy()
+        bad_q[3, 1, 2] = np.nan
+        set_f16 = lambda q, r: c.L.vsc_tn_set_fine_f16(c.ctx, None if q is None else q.ctypes.data,
+                                                       None if r is None else r.ctypes.data, 4, 8, 0, _lib.MEM_HOST)
+        assert set_f16(bad_q, good_r) == _lib.VSC_ERR_INVALID and b"query" in c.L.vsc_last_error()
+        assert c.L.vsc_tn_fine_bytes(c.ctx) == 0
+        assert set_f16(good_q, None) == 0
+        assert c.fine_similarity(pairs, True)[0] == _lib.VSC_ERR_INVALID and b"reference" in c.L.vsc_last_error()
+        assert set_f16(None, good_r) == 0
+        rc_, got, _ = c.fine_similarity(pairs, True)
+        half = lambda v: ref.half_rounded(v[:, :, :8])
+        assert rc_ == 0 and np.array_equal(helpers.bits(got[1]), helpers.bits(ref.fine_sim(half(qf[1]), half(rf[1]), "att", True)))
+    finally:
+        c.close()
+
+
+# The converted-rows upload (bin: {0, 1} bytes -> +-1 fp32 -> packed rows) works in chunks of 64 MB of fp32, host and device
+# sources alike: 262 144 rows at D = 64, which is 16 384 frames of 16 regions.  16 500 reference frames are the smallest
+# side that needs a second chunk; video 1 lies across the boundary (frame 20 of its 40 is the chunk's first), video 3 is
+# the last one, wholly inside the second chunk with the zero tail behind it.
+MC_REGIONS, MC_DIM, MC_CHUNK_FRAMES = 16, 64, (64 << 20) // (64 * 4) // 16
+MC_R_LENS = (MC_CHUNK_FRAMES - 20, 40, 60, 36)
+MC_Q_LENS = (5, 9)
+MC_PAIRS = [(0, 1), (1, 1), (0, 3), (1, 3)]
+
+
+def test_stage1_upload_in_more_than_one_chunk(gpu, orc):
+    import torch
+
+    from vsc2022_amd import _lib
+
+    assert sum(MC_R_LENS) == 16500 and sum(MC_R_LENS[:1]) < MC_CHUNK_FRAMES < sum(MC_R_LENS[:2])
+    rng = np.random.default_rng(16384)
+    qc, rc = [ref.unit_rows(rng, n, 8) for n in MC_Q_LENS], [ref.unit_rows(rng, n, 8) for n in MC_R_LENS]
+    q_rows = rng.integers(0, 2, size=(sum(MC_Q_LENS), MC_REGIONS, MC_DIM), dtype=np.uint8)
+    r_rows = rng.integers(0, 2, size=(sum(MC_R_LENS), MC_REGIONS, MC_DIM), dtype=np.uint8)
+    qf, rf = np.split(q_rows, np.cumsum(MC_Q_LENS)[:-1]), np.split(r_rows, np.cumsum(MC_R_LENS)[:-1])
+    want = {symmetric: [ref.fine_sim(qf[q], rf[r], "bin", symmetric) for q, r in MC_PAIRS] for symmetric in (False, True)}
+    # include/vscmi.h: round_up(frames R + 64, 128) rows of round_up(fdim, 64) floats per side
+    fine_bytes = sum((n * MC_REGIONS + 64 + 127) // 128 * 128 * 64 * 4 for n in (sum(MC_Q_LENS), sum(MC_R_LENS)))
+    c = Ctx(qc, rc)
+    try:
+        for mem in ("host", "device"):
+            if mem == "host":
+                q_ptr, r_ptr, mem_id = q_rows.ctypes.data, r_rows.ctypes.data, _lib.MEM_HOST
+            else:
+                keep = torch.from_numpy(q_rows).to("cuda:0"), torch.from_numpy(r_rows).to("cuda:0")
+                torch.cuda.synchronize()
+                q_ptr, r_ptr, mem_id = keep[0].data_ptr(), keep[1].data_ptr(), _lib.MEM_DEVICE
+            _lib.check(c.L.vsc_tn_set_fine(c.ctx, q_ptr, r_ptr, MC_REGIONS, MC_DIM, _lib.FINE_BIN, mem_id))
+            assert c.L.vsc_tn_fine_bytes(c.ctx) == fine_bytes
+            for symmetric in (False, True):
+                rc_, got, _ = c.fine_similarity(MC_PAIRS, symmetric)
+                assert rc_ == 0, c.L.vsc_last_error()
+                for p, a, b in zip(MC_PAIRS, got, want[symmetric]):
+                    assert np.array_equal(helpers.bits(a), helpers.bits(b)), (mem, p, symmetric, np.abs(a - b).max())
+            # (the second upload must not pass on the first one's rows: both sides are overwritten in between)
+            c.set_fine([np.zeros_like(v) for v in qf], [np.zeros_like(v) for v in rf], "bin")
+            assert not np.array_equal(c.fine_similarity(MC_PAIRS[:1], True)[1][0], want[True][0])
+    finally:
+        c.close()
+
+
 # ---- 2. stage 2 bits ------------------------------------------------------------------------------------------------
 
 S2_Q_LENS = (40, 25, 64, 12, 300, 0, 70)

@@ -61,16 +61,49 @@ int pack_into(const float* x, int64_t n, int dim, int mem, float* dst, int64_t r
         return VSC_OK;
     }
     const int64_t chunk_rows = std::max<int64_t>(1, (int64_t)(256ll << 20) / ((int64_t)dim * 4));
-    VSC_TRY(ws.stage.reserve((size_t)std::min(chunk_rows, n) * dim * 4));
-    for (int64_t r0 = 0; r0 < n; r0 += chunk_rows) {
-        const int64_t rows = std::min(chunk_rows, n - r0);
-        VSC_HIP(hipMemcpyAsync(ws.stage.p, x + r0 * dim, (size_t)rows * dim * 4, hipMemcpyHostToDevice, stream));
-        const bool last = (r0 + rows == n);
-        const int64_t out_rows = last ? rows_out - r0 : rows;
-        VSC_TRY(launch_pack_rows(ws.stage.as<float>(), rows, dim, dst + r0 * dpad, out_rows, dpad, stream, kpad));
-        if (h.rows) VSC_TRY(pack_half_any(ws.stage.as<float>(), rows, dim, h, r0, last ? h.rows_out - r0 : rows, stream));
-        VSC_HIP(hipStreamSynchronize(stream));  // staging buffer is reused
-    }
+    return for_row_chunks(ws, stream, x, (size_t)dim * 4, mem, n, rows_out, chunk_rows, false, [&](const void* src, const RowPiece& p) {
+        const float* rows = static_cast<const float*>(src);
+        VSC_TRY(launch_pack_rows(rows, p.rows, dim, dst + p.r0 * dpad, p.rows_out, dpad, stream, kpad));
+        // (the half image has a zero tail of its own)
+        if (h.rows) VSC_TRY(pack_half_any(rows, p.rows, dim, h, p.r0, p.r0 + p.rows == n ? h.rows_out - p.r0 : p.rows, stream));
+        return VSC_OK;
+    });
+}
+
+int pack_converted(Workspace& ws, hipStream_t stream, const void* x, size_t esz, ConvertRows convert, int64_t n, int dim, int mem,
+                   float* dst, int64_t rows_out, int dpad, const HalfImage& h) {
+    const int64_t chunk_rows = std::max<int64_t>(1, (int64_t)(64ll << 20) / ((int64_t)dim * 4));
+    VSC_TRY(ws.dec.reserve((size_t)std::min(chunk_rows, n) * dim * 4));
+    float* dec = ws.dec.as<float>();
+    return for_row_chunks(ws, stream, x, (size_t)dim * esz, mem, n, rows_out, chunk_rows, true, [&](const void* src, const RowPiece& p) {
+        VSC_TRY(convert(src, p.rows * dim, dec, stream));
+        VSC_TRY(launch_pack_rows(dec, p.rows, dim, dst + p.r0 * dpad, p.rows_out, dpad, stream));
+        if (h.rows) VSC_TRY(pack_half_any(dec, p.rows, dim, h, p.r0, p.r0 + p.rows == n ? h.rows_out - p.r0 : p.rows, stream));
+        return VSC_OK;
+    });
+}
+
+int half_rows_to_float(const void* src, int64_t elems, float* dst, hipStream_t stream) {
+    return launch_half_to_float(static_cast<const _Float16*>(src), elems, dst, stream);
+}
+
+int encode_rows(Workspace& ws, hipStream_t stream, const void* x, bool src16, int64_t n, int dim, int mem, int64_t chunk_rows,
+                _Float16* image, float* norms, int64_t row0, int64_t rows_out, int dpadh, bool frag, bool* refused) {
+    *refused = false;
+    VSC_TRY(ws.flag.reserve(16));
+    int* d_bad = ws.flag.as<int>();
+    VSC_HIP(hipMemsetAsync(d_bad, 0, sizeof(int), stream));
+    // (the largest piece: the last one, with the zero tail)
+    if (!norms) VSC_TRY(ws.qn.reserve((size_t)(std::min(chunk_rows, n) + rows_out - n) * 4));
+    VSC_TRY(for_row_chunks(ws, stream, x, (size_t)dim * (src16 ? 2 : 4), mem, n, rows_out, chunk_rows, false, [&](const void* src, const RowPiece& p) {
+        return launch_encode_rows(src, src16, p.rows, dim, image, norms ? norms + p.r0 : ws.qn.as<float>(), row0 + p.r0, p.rows_out, dpadh,
+                                  frag, d_bad, stream);
+    }));
+    int bad = 0;
+    VSC_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, stream));
+    VSC_HIP(hipStreamSynchronize(stream));
+    if (!norms) ws.qn.release();
+    *refused = bad != 0;
     return VSC_OK;
 }
 
@@ -599,63 +632,21 @@ static int i8_after_add(vsc_index* idx, int64_t first_new, int64_t n, int64_t ne
 }
 
 // SQfp16 handle: rows [ntotal, ntotal + n) of the store from fp32 or fp16 rows (host sources staged in chunks of their
-// own element size: fp16 rows never exist as fp32 anywhere), rows up to `need_rows` zero filled.  A row fp16 cannot
-// hold fails the add: what was written is zero filled again, the index is as it was.
+// own element size: fp16 rows never exist as fp32 anywhere; device sources in one launch), rows up to `need_rows` zero
+// filled.  A row fp16 cannot hold fails the add: what was written is zero filled again, the index is as it was.
 static int store_rows(vsc_index* idx, const void* x, bool src16, int64_t n, int x_mem, int64_t need_rows) {
-    const size_t esz = src16 ? 2 : 4;
-    Workspace& ws = idx->ws;
-    VSC_TRY(ws.flag.reserve(16));
-    int* d_bad = ws.flag.as<int>();
-    VSC_HIP(hipMemsetAsync(d_bad, 0, sizeof(int), idx->stream));
     _Float16* image = idx->refh.as<_Float16>();
-    float* norms = idx->refn.as<float>();
+    float* norms = idx->refn.as<float>() + idx->ntotal;
     const int64_t first = idx->ntotal, rows_out = need_rows - first;
-    if (x_mem == VSC_MEM_DEVICE) {
-        VSC_TRY(launch_encode_rows(x, src16, n, idx->dim, image, norms + first, first, rows_out, idx->dpadh, idx->frag, d_bad, idx->stream));
-    } else {
-        const int64_t chunk_rows = std::max<int64_t>(1, (int64_t)(256ll << 20) / ((int64_t)idx->dim * (int64_t)esz));
-        VSC_TRY(ws.stage.reserve((size_t)std::min(chunk_rows, n) * idx->dim * esz));
-        for (int64_t r0 = 0; r0 < n; r0 += chunk_rows) {
-            const int64_t rows = std::min(chunk_rows, n - r0);
-            VSC_HIP(hipMemcpyAsync(ws.stage.p, static_cast<const char*>(x) + (size_t)r0 * idx->dim * esz, (size_t)rows * idx->dim * esz,
-                                   hipMemcpyHostToDevice, idx->stream));
-            const bool last = r0 + rows == n;
-            VSC_TRY(launch_encode_rows(ws.stage.p, src16, rows, idx->dim, image, norms + first + r0, first + r0,
-                                       last ? rows_out - r0 : rows, idx->dpadh, idx->frag, d_bad, idx->stream));
-            VSC_HIP(hipStreamSynchronize(idx->stream));  // staging buffer is reused
-        }
-    }
-    int bad = 0;
-    VSC_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, idx->stream));
-    VSC_HIP(hipStreamSynchronize(idx->stream));
-    if (bad) {
-        VSC_TRY(launch_encode_rows(nullptr, src16, 0, idx->dim, image, norms + first, first, rows_out, idx->dpadh, idx->frag, d_bad, idx->stream));
+    const int64_t chunk_rows = std::max<int64_t>(1, x_mem == VSC_MEM_DEVICE ? n : (int64_t)(256ll << 20) / ((int64_t)idx->dim * (src16 ? 2 : 4)));
+    bool refused = false;
+    VSC_TRY(encode_rows(idx->ws, idx->stream, x, src16, n, idx->dim, x_mem, chunk_rows, image, norms, first, rows_out, idx->dpadh,
+                        idx->frag, &refused));
+    if (refused) {
+        VSC_TRY(launch_encode_rows(nullptr, src16, 0, idx->dim, image, norms, first, rows_out, idx->dpadh, idx->frag, idx->ws.flag.as<int>(), idx->stream));
         VSC_HIP(hipStreamSynchronize(idx->stream));
         set_error("vsc_index_add: a row holds NaN, +-inf or a value beyond +-65504, which the SQfp16 codec cannot store; nothing was added");
         return VSC_ERR_INVALID;
-    }
-    return VSC_OK;
-}
-
-// Flat handle, fp16 rows: decoded in bounded chunks (ws.dec) and packed like fp32 rows -- the result of `add` of the
-// upcast array.
-static int pack_f16_rows(vsc_index* idx, const uint16_t* x, int64_t n, int x_mem, float* dst, int64_t rows_out, const HalfImage& h) {
-    Workspace& ws = idx->ws;
-    const int64_t chunk_rows = std::max<int64_t>(1, (int64_t)(64ll << 20) / ((int64_t)idx->dim * 4));
-    VSC_TRY(ws.dec.reserve((size_t)std::min(chunk_rows, n) * idx->dim * 4));
-    if (x_mem != VSC_MEM_DEVICE) VSC_TRY(ws.stage.reserve((size_t)std::min(chunk_rows, n) * idx->dim * 2));
-    for (int64_t r0 = 0; r0 < n; r0 += chunk_rows) {
-        const int64_t rows = std::min(chunk_rows, n - r0);
-        const uint16_t* src = x + r0 * idx->dim;
-        if (x_mem != VSC_MEM_DEVICE) {
-            VSC_HIP(hipMemcpyAsync(ws.stage.p, src, (size_t)rows * idx->dim * 2, hipMemcpyHostToDevice, idx->stream));
-            src = ws.stage.as<uint16_t>();
-        }
-        VSC_TRY(launch_half_to_float(reinterpret_cast<const _Float16*>(src), rows * idx->dim, ws.dec.as<float>(), idx->stream));
-        const bool last = r0 + rows == n;
-        VSC_TRY(launch_pack_rows(ws.dec.as<float>(), rows, idx->dim, dst + r0 * idx->dpad, last ? rows_out - r0 : rows, idx->dpad, idx->stream));
-        if (h.rows) VSC_TRY(pack_half_any(ws.dec.as<float>(), rows, idx->dim, h, r0, last ? h.rows_out - r0 : rows, idx->stream));
-        VSC_HIP(hipStreamSynchronize(idx->stream));  // the buffers are reused
     }
     return VSC_OK;
 }
@@ -732,7 +723,8 @@ static int index_add(vsc_index_t* idx, const void* x, bool src16, int64_t n, int
         h.rows_out = need_rows - idx->ntotal;
         h.dpadh = idx->dpadh;
     }
-    if (src16) VSC_TRY(pack_f16_rows(idx, static_cast<const uint16_t*>(x), n, x_mem, dst, need_rows - idx->ntotal, h));
+    // (fp16 rows of a Flat handle: decoded in bounded chunks and packed like fp32 rows -- the result of `add` of the upcast array)
+    if (src16) VSC_TRY(pack_converted(idx->ws, idx->stream, x, 2, half_rows_to_float, n, idx->dim, x_mem, dst, need_rows - idx->ntotal, idx->dpad, h));
     else VSC_TRY(pack_into(static_cast<const float*>(x), n, idx->dim, x_mem, dst, need_rows - idx->ntotal, idx->dpad, idx->ws, idx->stream, h));
     VSC_HIP(hipStreamSynchronize(idx->stream));
     idx->ntotal += n;  // (the int8 image catches up in i8_prepare, before the next search)

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "row_chunks.h"
 
 namespace vscmi {
 
@@ -66,6 +67,44 @@ struct HalfImage {
 int pack_half_any(const float* x, int64_t n, int dim, const HalfImage& h, int64_t r0, int64_t rows_out, hipStream_t stream);
 int pack_into(const float* x, int64_t n, int dim, int mem, float* dst, int64_t rows_out, int dpad, Workspace& ws,
               hipStream_t stream, const HalfImage& h = HalfImage(), float kpad = 0.0f);
+
+// The one staging loop of the row uploads (api.hip, api_tn.hip): `n` rows of row_bytes bytes at x (in `mem`) -> rows_out
+// rows of some image, in the pieces of row_chunks.h.  fn(src, piece) launches what writes the piece's rows_out rows; src
+// is the device address of the piece's source rows (nullptr: it has none) -- the caller's own memory, or ws.stage,
+// which a host source goes through (reserved once).  The stream is synchronised after a piece that was staged, and after
+// every piece with source rows when the caller's own scratch is reused between them (`scratch_reused`: ws.dec).
+template <class Fn>
+int for_row_chunks(Workspace& ws, hipStream_t stream, const void* x, size_t row_bytes, int mem, int64_t n, int64_t rows_out,
+                   int64_t chunk_rows, bool scratch_reused, Fn fn) {
+    const bool host = mem != VSC_MEM_DEVICE;
+    if (host && n > 0) VSC_TRY(ws.stage.reserve((size_t)std::min(chunk_rows, n) * row_bytes));
+    for (int64_t r0 = 0; r0 < rows_out;) {
+        const RowPiece p = row_piece(r0, n, rows_out, chunk_rows);
+        const void* src = p.rows ? static_cast<const char*>(x) + (size_t)r0 * row_bytes : nullptr;
+        const bool staged = host && p.rows;
+        if (staged) {
+            VSC_HIP(hipMemcpyAsync(ws.stage.p, src, (size_t)p.rows * row_bytes, hipMemcpyHostToDevice, stream));
+            src = ws.stage.p;
+        }
+        VSC_TRY(fn(src, p));
+        if (staged || (scratch_reused && p.rows)) VSC_HIP(hipStreamSynchronize(stream));
+        r0 += p.rows_out;
+    }
+    return VSC_OK;
+}
+// Rows of `dim` elements of esz bytes that are not fp32 yet (fp16 rows of a Flat store, {0, 1} bytes of a bin fine store)
+// -> packed fp32 rows of dpad floats at dst (+ the optional half image), as pack_into of the converted array.  In
+// chunks of <= 64 MB of fp32, device sources too: convert(src, elements, ws.dec, stream), then packed like every other row.
+typedef int (*ConvertRows)(const void* src, int64_t elems, float* dst, hipStream_t stream);
+int pack_converted(Workspace& ws, hipStream_t stream, const void* x, size_t esz, ConvertRows convert, int64_t n, int dim, int mem,
+                   float* dst, int64_t rows_out, int dpad, const HalfImage& h = HalfImage());
+int half_rows_to_float(const void* src, int64_t elems, float* dst, hipStream_t stream);  // the ConvertRows of fp16 rows
+// Half-float rows [row0, row0 + rows_out) of `image` (dpadh halves each, fragment-major if `frag`) from n fp32 or fp16
+// rows by the SQfp16 encoder (codec_f16.hip), those from n on as zeros, in chunks of chunk_rows source rows of their own
+// element size.  norms: the rows' norm bounds, rows_out of them -- or nullptr: nobody wants them, they go to ws.qn,
+// which is released again.  *refused: an element was NaN, +-inf or beyond +-65504; the caller names it and cleans up.
+int encode_rows(Workspace& ws, hipStream_t stream, const void* x, bool src16, int64_t n, int dim, int mem, int64_t chunk_rows,
+                _Float16* image, float* norms, int64_t row0, int64_t rows_out, int dpadh, bool frag, bool* refused);
 
 // The state of the entry points that own no handle, one per device for the life of the process (api_aux.hip; also behind
 // vsc_tn_forward_sim / vsc_align_forward_sim in api_tn.hip).  A call holds `mu` from its first use of the context on.

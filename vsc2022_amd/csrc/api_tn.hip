@@ -1,8 +1,9 @@
 // C ABI of libvscmi.so, part 5: the Temporal-Network localisation contexts (vsc_tn_*), the DTW / DP aligners on them
 // (vsc_tn_align), the handle-less forms of both over caller matrices (vsc_tn_forward_sim, vsc_align_forward_sim), the
 // match-rows stage behind them (vsc_tn_set_timestamps, vsc_tn_match_rows) and the DnS fine descriptors (vsc_tn_set_fine,
-// vsc_tn_set_fine_bits, vsc_tn_set_fine_f16, vsc_tn_fine_similarity, vsc_tn_localize_fine, vsc_tn_similarity_fine).  Host plumbing only: the
-// kernels are in tn.hip, align.hip, match_rows.hip, fine_sim.hip and fine_bits.hip.
+// vsc_tn_set_fine_bits, vsc_tn_set_fine_f16 -- one FineStore, written by tn_set_fine --, vsc_tn_fine_similarity,
+// vsc_tn_localize_fine, vsc_tn_similarity_fine).  Host plumbing only: the kernels are in tn.hip, align.hip, match_rows.hip,
+// fine_sim.hip and fine_bits.hip; rows come up through the staging loop of api_internal.h (for_row_chunks).
 #include "api_internal.h"
 
 // ------------------------------------------------------------------------ TN launches
@@ -235,6 +236,15 @@ static int upload_sims(DeviceCtx* c, const float* sims, const int64_t* sims_off,
 
 // ------------------------------------------------------------------------ TN context
 
+// The DnS fine descriptors of a context (tn_set_fine): `regions` rows of row_bytes bytes per frame of either side.
+// VSC_FINE_ATT / VSC_FINE_BIN (vsc_tn_set_fine): packed fp32 rows of round_up(dim, K_PAD) floats (bin: +-1);
+// VSC_FINE_F16 (vsc_tn_set_fine_f16): as many half floats, natural k order; VSC_FINE_BITS (vsc_tn_set_fine_bits): bit rows
+// of fine_bits_row_words(dim) 16-byte words.
+struct FineStore {
+    int kind = -1, regions = 0, dim = 0, row_bytes = 0;
+    struct Side { DevBuf rows; bool has = false; int64_t bytes = 0; } side[2];  // query, reference
+};
+
 struct vsc_tn_ctx {
     int device = 0, dim = 0, dpad = 0;
     // VSC_CODEC_FLAT: `rfeat` holds the packed fp32 reference rows.  VSC_CODEC_SQFP16: `rfeat` is never allocated; the
@@ -250,15 +260,11 @@ struct vsc_tn_ctx {
     // [rows][2], the scan's scratch and control words, and the row columns when the caller wants them on the host
     DevBuf d_qts, d_rts, d_rowoff, d_tileoff, d_rowctl, d_rows[4];
     bool has_qts = false, has_rts = false;
-    // DnS fine descriptors (vsc_tn_set_fine): fine_regions packed fp32 rows of fine_dpad floats per frame of either side
-    // (bin: +-1) -- or, fine_kind == VSC_FINE_BITS (vsc_tn_set_fine_bits), bit rows of fine_w16 16-byte words in the same
-    // buffers, or, fine_kind == VSC_FINE_F16 (vsc_tn_set_fine_f16), rows of fine_dpad half floats in natural k order --,
-    // the scratch of vsc_tn_fine_similarity (work list, offsets, error word, dense output for host callers)
-    // and of vsc_tn_localize_fine / vsc_tn_similarity_fine (the fine slab of host callers, its offsets, frame counts)
-    int fine_regions = 0, fine_dim = 0, fine_dpad = 0, fine_w16 = 0, fine_kind = -1;
-    bool has_qfine = false, has_rfine = false;
-    int64_t qfine_bytes = 0, rfine_bytes = 0;
-    DevBuf qfine, rfine, d_fwork, d_foff, d_ferr, fine_out, fine_mat, d_flq, d_flr;
+    // DnS: the fine descriptors, the scratch of vsc_tn_fine_similarity (work list, offsets, error word, dense output for
+    // host callers) and of vsc_tn_localize_fine / vsc_tn_similarity_fine (the fine slab of host callers, its offsets,
+    // frame counts)
+    FineStore fine;
+    DevBuf d_fwork, d_foff, d_ferr, fine_out, fine_mat, d_flq, d_flr;
     Workspace ws;
     hipStream_t stream = nullptr;      // own_stream, or the caller's (vsc_tn_set_stream)
     hipStream_t own_stream = nullptr;
@@ -279,28 +285,34 @@ static void bind_ctx(Args& a, const vsc_tn_ctx* c, float bias) {
     a.bias = bias;
 }
 
-// `n` rows of `dim` elements of `esz` bytes that are not fp32 yet -> packed fp32 rows of dpad floats at dst (rows_out
-// written, those from n on as zeros).  In chunks of <= 64 MB of fp32: staged (ws.stage, host sources), brought to fp32 by
-// `convert(src, elements, dst, stream)` (ws.dec), packed like every other row upload.
-template <class Convert>
-static int tn_pack_converted(vsc_tn_ctx* c, const void* x, size_t esz, int64_t n, int dim, int dpad, int mem, float* dst,
-                             int64_t rows_out, Convert convert) {
-    if (n == 0) return launch_pack_rows(nullptr, 0, dim, dst, rows_out, dpad, c->stream);
-    Workspace& ws = c->ws;
-    const int64_t chunk_rows = std::max<int64_t>(1, (int64_t)(64ll << 20) / ((int64_t)dim * 4));
-    VSC_TRY(ws.dec.reserve((size_t)std::min(chunk_rows, n) * dim * 4));
-    if (mem != VSC_MEM_DEVICE) VSC_TRY(ws.stage.reserve((size_t)std::min(chunk_rows, n) * dim * esz));
-    for (int64_t r0 = 0; r0 < n; r0 += chunk_rows) {
-        const int64_t rows = std::min(chunk_rows, n - r0);
-        const void* src = static_cast<const char*>(x) + (size_t)r0 * dim * esz;
-        if (mem != VSC_MEM_DEVICE) {
-            VSC_HIP(hipMemcpyAsync(ws.stage.p, src, (size_t)rows * dim * esz, hipMemcpyHostToDevice, c->stream));
-            src = ws.stage.p;
-        }
-        VSC_TRY(convert(src, rows * dim, ws.dec.as<float>(), c->stream));
-        VSC_TRY(launch_pack_rows(ws.dec.as<float>(), rows, dim, dst + r0 * dpad, r0 + rows == n ? rows_out - r0 : rows, dpad, c->stream));
-        VSC_HIP(hipStreamSynchronize(c->stream));  // the buffers are reused
+// What vsc_tn_set_fine, vsc_tn_set_fine_bits and vsc_tn_set_fine_f16 do once their arguments have passed: the store takes
+// the new description, and each side that is given is written by write(side, x, rows, dst, rows_out) -- `rows` source
+// rows at x -> rows_out rows at dst, those from `rows` on as zeros.  A side that is being replaced is not held, and
+// counts 0 bytes, until its new rows are down -- for good if `write` fails: no half-written side is read.
+template <class Write>
+static int tn_set_fine(vsc_tn_ctx* c, int kind, int regions, int fdim, int row_bytes, const void* qfine, const void* rfine, Write write) {
+    VSC_HIP(hipSetDevice(c->device));
+    FineStore& f = c->fine;
+    const void* x[2] = {qfine, rfine};
+    const int64_t frames[2] = {c->q_off.back(), c->r_off.back()};
+    // a side kept from another shape or kind could not meet the new one: both are dropped before anything can fail, the
+    // ones given come back below
+    if (regions != f.regions || fdim != f.dim || kind != f.kind)
+        for (FineStore::Side& s : f.side) s.has = false, s.bytes = 0;
+    f.kind = kind, f.regions = regions, f.dim = fdim, f.row_bytes = row_bytes;
+    for (int k = 0; k < 2; ++k) {
+        FineStore::Side& s = f.side[k];
+        if (!x[k]) continue;
+        s.has = false, s.bytes = 0;  // (until the new rows are down)
+        const int64_t rows = frames[k] * regions;
+        // +64 rows of slack, zeroed: the 64-row tiles of the last video's last frames read past its end (fine_sim.hip, fine_bits.hip)
+        const int64_t rows_out = round_up64(rows + 64, ROW_PAD);
+        VSC_TRY(s.rows.reserve((size_t)rows_out * row_bytes));
+        VSC_TRY(write(k, x[k], rows, s.rows.p, rows_out));
+        s.bytes = rows_out * row_bytes;
+        s.has = true;
     }
+    VSC_HIP(hipStreamSynchronize(c->stream));
     return VSC_OK;
 }
 
@@ -318,47 +330,14 @@ int vsc_tn_set_stream(vsc_tn_ctx_t* c, void* hip_stream, int own) {
     return VSC_OK;
 }
 
-// Flat context, reference rows handed over as half floats: the context of the upcast array
-static int tn_pack_f16_rows(vsc_tn_ctx* c, const uint16_t* x, int64_t n, int mem, float* dst, int64_t rows_out) {
-    return tn_pack_converted(c, x, 2, n, c->dim, c->dpad, mem, dst, rows_out, [](const void* src, int64_t elems, float* out, hipStream_t s) {
-        return launch_half_to_float(static_cast<const _Float16*>(src), elems, out, s);
-    });
-}
-
-// Half-float rows at `image` ([r_rows][dpad] halves) from `n` fp32 or fp16 rows of `dim` elements, by the index codec's
-// encoder (codec_f16.hip: round to nearest even, subnormals kept, natural layout): the reference store of an SQfp16
-// context (tn_store_rows) and a side of a VSC_FINE_F16 fine store (vsc_tn_set_fine_f16).  All r_rows rows are written,
-// those from n on as zeros.  Host sources are staged in chunks of their own element size: no fp32 image of the rows
-// exists at any time.  The encoder's per-row norm bounds are of no use here and go to a scratch buffer of one chunk
-// (ws.qn).  *refused: an element was NaN, +-inf or beyond +-65504 -- the caller names it and drops what was written.
+// Half-float rows at `image` ([r_rows][dpad] halves, natural layout) from `n` fp32 or fp16 rows of `dim` elements, by the
+// index codec's encoder (encode_rows): the reference store of an SQfp16 context and a side of a VSC_FINE_F16 fine store
+// (vsc_tn_set_fine_f16).  All r_rows rows are written, those from n on as zeros; device sources are chunked like host
+// sources; nobody reads the encoder's norm bounds.  *refused: the caller names it and drops what was written.
 static int tn_encode_rows(vsc_tn_ctx* c, const void* x, bool src16, int64_t n, int dim, int dpad, int mem, _Float16* image,
                           int64_t r_rows, bool* refused) {
-    const size_t esz = src16 ? 2 : 4;
-    Workspace& ws = c->ws;
-    *refused = false;
-    VSC_TRY(ws.flag.reserve(16));
-    int* d_bad = ws.flag.as<int>();
-    VSC_HIP(hipMemsetAsync(d_bad, 0, sizeof(int), c->stream));
-    const int64_t chunk_rows = std::max<int64_t>(ROW_PAD, (int64_t)(256ll << 20) / ((int64_t)dim * (int64_t)esz));
-    VSC_TRY(ws.qn.reserve((size_t)std::min(chunk_rows, r_rows) * 4));
-    const bool host = mem != VSC_MEM_DEVICE;
-    if (host && n > 0) VSC_TRY(ws.stage.reserve((size_t)std::min(chunk_rows, n) * dim * esz));
-    for (int64_t r0 = 0; r0 < r_rows; r0 += chunk_rows) {
-        const int64_t rows_out = std::min(chunk_rows, r_rows - r0);
-        const int64_t rows = std::max<int64_t>(0, std::min(rows_out, n - r0));  // source rows of the chunk
-        const void* src = rows ? static_cast<const char*>(x) + (size_t)r0 * dim * esz : nullptr;
-        if (host && rows) {
-            VSC_HIP(hipMemcpyAsync(ws.stage.p, src, (size_t)rows * dim * esz, hipMemcpyHostToDevice, c->stream));
-            src = ws.stage.p;
-        }
-        VSC_TRY(launch_encode_rows(src, src16, rows, dim, image, ws.qn.as<float>(), r0, rows_out, dpad, false, d_bad, c->stream));
-        if (host) VSC_HIP(hipStreamSynchronize(c->stream));  // the staging buffer is reused
-    }
-    int bad = 0;
-    VSC_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    VSC_HIP(hipStreamSynchronize(c->stream));
-    *refused = bad != 0;
-    return VSC_OK;
+    const int64_t chunk_rows = std::max<int64_t>(ROW_PAD, (int64_t)(256ll << 20) / ((int64_t)dim * (src16 ? 2 : 4)));
+    return encode_rows(c->ws, c->stream, x, src16, n, dim, mem, chunk_rows, image, nullptr, 0, r_rows, dpad, false, refused);
 }
 
 static int tn_store_rows(vsc_tn_ctx* c, const void* x, bool src16, int64_t n, int mem, int64_t r_rows) {
@@ -411,11 +390,11 @@ int vsc_tn_create_codec(const float* qfeat, const int64_t* q_off, int64_t n_qvid
         c->ref_bytes = r_rows * c->dpad * 2;
         if ((rc = c->rfeat_h.reserve((size_t)c->ref_bytes)) != VSC_OK) return fail(rc);
         if ((rc = tn_store_rows(c, rfeat, ref_f16 != 0, nr, ref_mem, r_rows)) != VSC_OK) return fail(rc);
-        c->ws.qn.release();  // (scratch of the encoder)
     } else {
         c->ref_bytes = r_rows * c->dpad * 4;
         if ((rc = c->rfeat.reserve((size_t)c->ref_bytes)) != VSC_OK) return fail(rc);
-        if (ref_f16) rc = tn_pack_f16_rows(c, static_cast<const uint16_t*>(rfeat), nr, ref_mem, c->rfeat.as<float>(), r_rows);
+        // (reference rows handed over as half floats: the context of the upcast array)
+        if (ref_f16) rc = pack_converted(c->ws, c->stream, rfeat, 2, half_rows_to_float, nr, dim, ref_mem, c->rfeat.as<float>(), r_rows, c->dpad);
         else rc = pack_into(static_cast<const float*>(rfeat), nr, dim, ref_mem, c->rfeat.as<float>(), r_rows, c->dpad, c->ws, c->stream);
         if (rc != VSC_OK) return fail(rc);
     }
@@ -446,8 +425,8 @@ int vsc_tn_set_queries(vsc_tn_ctx_t* c, const float* qfeat, const int64_t* q_off
     }
     VSC_HIP(hipSetDevice(c->device));
     c->has_qts = false;  // (the table described the rows that are being replaced: vsc_tn_set_timestamps)
-    c->has_qfine = false;  // (... and so did the fine descriptors: vsc_tn_set_fine)
-    c->qfine_bytes = 0;
+    c->fine.side[0].has = false;  // (... and so did the fine descriptors: vsc_tn_set_fine)
+    c->fine.side[0].bytes = 0;
     // everything that can fail (allocation, packing, upload) runs on local state first: the context keeps its old,
     // consistent query side if any of it does, and takes the new offsets only once the device holds the new rows
     std::vector<int64_t> off(q_off, q_off + n_qvid + 1);
@@ -901,104 +880,39 @@ int vsc_tn_similarity(vsc_tn_ctx_t* c, int32_t q_vid, int32_t r_vid, float bias,
 
 // ------------------------------------------------------------------------ DnS: fine descriptors, region Chamfer, blend
 
-// One side's fine descriptors -> `rows` packed fp32 rows at dst (rows_out written, those from `rows` on as zeros).  att:
-// fp32, packed like every other row upload; bin: {0, 1} bytes, converted to +-1 in bounded chunks first.
-static int tn_fine_store(vsc_tn_ctx* c, const void* x, int kind, int64_t rows, int mem, float* dst, int64_t rows_out) {
-    const int dim = c->fine_dim, dpad = c->fine_dpad;
-    if (kind == VSC_FINE_ATT) return pack_into(static_cast<const float*>(x), rows, dim, mem, dst, rows_out, dpad, c->ws, c->stream);
-    return tn_pack_converted(c, x, 1, rows, dim, dpad, mem, dst, rows_out, [](const void* src, int64_t elems, float* out, hipStream_t s) {
-        return launch_bin_to_pm1(static_cast<const uint8_t*>(src), elems, out, s);
-    });
-}
-
 int vsc_tn_set_fine(vsc_tn_ctx_t* c, const void* qfine, const void* rfine, int regions, int fdim, int kind, int mem) {
     if (!c || regions < 1 || regions > VSC_FINE_MAX_REGIONS || fdim < 1 || (kind != VSC_FINE_ATT && kind != VSC_FINE_BIN)) {
         set_error("vsc_tn_set_fine: invalid argument (regions 1..%d, fdim >= 1, kind VSC_FINE_ATT / VSC_FINE_BIN)", VSC_FINE_MAX_REGIONS);
         return VSC_ERR_INVALID;
     }
-    VSC_HIP(hipSetDevice(c->device));
-    if (regions != c->fine_regions || fdim != c->fine_dim || kind != c->fine_kind) {
-        // a side kept from another shape or kind could not meet the new one: both are dropped, the one given comes back below
-        c->has_qfine = c->has_rfine = false;
-        c->qfine_bytes = c->rfine_bytes = 0;
-    }
-    c->fine_regions = regions;
-    c->fine_dim = fdim;
-    c->fine_kind = kind;
-    c->fine_dpad = round_up(fdim, K_PAD);
-    struct Side { const void* x; int64_t frames; DevBuf* buf; bool* has; int64_t* bytes; };
-    Side sides[2] = {{qfine, c->q_off.back(), &c->qfine, &c->has_qfine, &c->qfine_bytes},
-                     {rfine, c->r_off.back(), &c->rfine, &c->has_rfine, &c->rfine_bytes}};
-    for (Side& s : sides) {
-        if (!s.x) continue;
-        *s.has = false;  // (until the new rows are down)
-        const int64_t rows = s.frames * regions;
-        // +64 rows of slack: the 64-row tiles of the last video's last frames read past its end (fine_sim.hip)
-        const int64_t rows_out = round_up64(rows + 64, ROW_PAD);
-        VSC_TRY(s.buf->reserve((size_t)rows_out * c->fine_dpad * 4));
-        VSC_TRY(tn_fine_store(c, s.x, kind, rows, mem, s.buf->as<float>(), rows_out));
-        *s.bytes = rows_out * c->fine_dpad * 4;
-        *s.has = true;
-    }
-    VSC_HIP(hipStreamSynchronize(c->stream));
-    return VSC_OK;
+    const int dpad = round_up(fdim, K_PAD);
+    return tn_set_fine(c, kind, regions, fdim, dpad * 4, qfine, rfine, [&](int, const void* x, int64_t rows, void* dst, int64_t rows_out) {
+        // att: fp32, packed like every other row upload; bin: {0, 1} bytes, converted to +-1 in bounded chunks first
+        if (kind == VSC_FINE_ATT)
+            return pack_into(static_cast<const float*>(x), rows, fdim, mem, static_cast<float*>(dst), rows_out, dpad, c->ws, c->stream);
+        const ConvertRows to_pm1 = [](const void* src, int64_t elems, float* out, hipStream_t s) {
+            return launch_bin_to_pm1(static_cast<const uint8_t*>(src), elems, out, s);
+        };
+        return pack_converted(c->ws, c->stream, x, 1, to_pm1, rows, fdim, mem, static_cast<float*>(dst), rows_out, dpad);
+    });
 }
 
-// One side's bit rows (VSC_FINE_BITS): `rows` source rows -- fine_dim bytes {0, 1} each, or ceil(fine_dim / 8) packed
-// bytes -- -> rows_out rows of fine_w16 16-byte words at dst, those from `rows` on as zeros.  Host sources are staged in
-// chunks of <= 64 MB (ws.stage); a chunk is one launch.
-static int tn_fine_store_bits(vsc_tn_ctx* c, const void* x, bool packed, int64_t rows, int mem, uint32_t* dst, int64_t rows_out) {
-    const int dim = c->fine_dim, w16 = c->fine_w16;
-    const int64_t src_row = packed ? (dim + 7) / 8 : dim;
-    const int64_t chunk_rows = std::max<int64_t>(1, (int64_t)(64ll << 20) / std::max<int64_t>(src_row, 16 * (int64_t)w16));
-    const bool host = mem != VSC_MEM_DEVICE;
-    if (host && rows > 0) VSC_TRY(c->ws.stage.reserve((size_t)(std::min(chunk_rows, rows) * src_row)));
-    for (int64_t r0 = 0; r0 < rows_out; r0 += chunk_rows) {
-        const int64_t n_out = std::min(chunk_rows, rows_out - r0);
-        const int64_t n = std::max<int64_t>(0, std::min(n_out, rows - r0));  // source rows of the chunk
-        const void* src = n ? static_cast<const char*>(x) + (size_t)(r0 * src_row) : nullptr;
-        if (host && n) {
-            VSC_HIP(hipMemcpyAsync(c->ws.stage.p, src, (size_t)(n * src_row), hipMemcpyHostToDevice, c->stream));
-            src = c->ws.stage.p;
-        }
-        VSC_TRY(launch_pack_bits(static_cast<const uint8_t*>(src), packed, n, dim, dst + r0 * 4 * w16, n_out, w16, c->stream));
-        if (host && n) VSC_HIP(hipStreamSynchronize(c->stream));  // the staging buffer is reused
-    }
-    return VSC_OK;
-}
-
+// Bit rows: fdim bytes {0, 1} per source row, or ceil(fdim / 8) packed bytes -> w16 16-byte words.  Chunks of <= 64 MB of
+// the larger of the two, device sources too; a chunk is one launch.
 int vsc_tn_set_fine_bits(vsc_tn_ctx_t* c, const void* qfine, const void* rfine, int regions, int fdim, int packed, int mem) {
     if (!c || regions < 1 || regions > VSC_FINE_MAX_REGIONS || fdim < 1 || fdim > (1 << 24) || (packed != 0 && packed != 1)) {
         set_error("vsc_tn_set_fine_bits: invalid argument (regions 1..%d, fdim 1..%d, packed 0 / 1)", VSC_FINE_MAX_REGIONS, 1 << 24);
         return VSC_ERR_INVALID;
     }
-    VSC_HIP(hipSetDevice(c->device));
-    if (regions != c->fine_regions || fdim != c->fine_dim || c->fine_kind != VSC_FINE_BITS) {
-        // (as vsc_tn_set_fine: a side kept from another shape or kind could not meet the new one)
-        c->has_qfine = c->has_rfine = false;
-        c->qfine_bytes = c->rfine_bytes = 0;
-    }
-    c->fine_regions = regions;
-    c->fine_dim = fdim;
-    c->fine_kind = VSC_FINE_BITS;
-    c->fine_dpad = 0;
-    c->fine_w16 = fine_bits_row_words(fdim);
-    struct Side { const void* x; int64_t frames; DevBuf* buf; bool* has; int64_t* bytes; };
-    Side sides[2] = {{qfine, c->q_off.back(), &c->qfine, &c->has_qfine, &c->qfine_bytes},
-                     {rfine, c->r_off.back(), &c->rfine, &c->has_rfine, &c->rfine_bytes}};
-    for (Side& s : sides) {
-        if (!s.x) continue;
-        *s.has = false;  // (until the new rows are down)
-        const int64_t rows = s.frames * regions;
-        // +64 rows of slack, zeroed: the 64-row tiles of the last video's last frames read past its end (fine_bits.hip)
-        const int64_t rows_out = round_up64(rows + 64, ROW_PAD);
-        VSC_TRY(s.buf->reserve((size_t)rows_out * c->fine_w16 * 16));
-        VSC_TRY(tn_fine_store_bits(c, s.x, packed != 0, rows, mem, s.buf->as<uint32_t>(), rows_out));
-        *s.bytes = rows_out * c->fine_w16 * 16;
-        *s.has = true;
-    }
-    VSC_HIP(hipStreamSynchronize(c->stream));
-    return VSC_OK;
+    const int w16 = fine_bits_row_words(fdim);
+    const int64_t src_row = packed ? (fdim + 7) / 8 : fdim;
+    const int64_t chunk_rows = std::max<int64_t>(1, (int64_t)(64ll << 20) / std::max<int64_t>(src_row, 16 * (int64_t)w16));
+    return tn_set_fine(c, VSC_FINE_BITS, regions, fdim, w16 * 16, qfine, rfine, [&](int, const void* x, int64_t rows, void* dst, int64_t rows_out) {
+        return for_row_chunks(c->ws, c->stream, x, (size_t)src_row, mem, rows, rows_out, chunk_rows, false, [&](const void* src, const RowPiece& p) {
+            return launch_pack_bits(static_cast<const uint8_t*>(src), packed != 0, p.rows, fdim, static_cast<uint32_t*>(dst) + p.r0 * 4 * w16,
+                                    p.rows_out, w16, c->stream);
+        });
+    });
 }
 
 int vsc_tn_set_fine_f16(vsc_tn_ctx_t* c, const void* qfine, const void* rfine, int regions, int fdim, int src_f16, int mem) {
@@ -1006,43 +920,21 @@ int vsc_tn_set_fine_f16(vsc_tn_ctx_t* c, const void* qfine, const void* rfine, i
         set_error("vsc_tn_set_fine_f16: invalid argument (regions 1..%d, fdim >= 1, src_f16 0 / 1)", VSC_FINE_MAX_REGIONS);
         return VSC_ERR_INVALID;
     }
-    VSC_HIP(hipSetDevice(c->device));
-    if (regions != c->fine_regions || fdim != c->fine_dim || c->fine_kind != VSC_FINE_F16) {
-        // (as vsc_tn_set_fine: a side kept from another shape or kind could not meet the new one)
-        c->has_qfine = c->has_rfine = false;
-        c->qfine_bytes = c->rfine_bytes = 0;
-    }
-    c->fine_regions = regions;
-    c->fine_dim = fdim;
-    c->fine_kind = VSC_FINE_F16;
-    c->fine_dpad = round_up(fdim, K_PAD);  // (halves per row: a multiple of 128 bytes, every 16-byte piece aligned)
-    struct Side { const void* x; int64_t frames; DevBuf* buf; bool* has; int64_t* bytes; const char* name; };
-    Side sides[2] = {{qfine, c->q_off.back(), &c->qfine, &c->has_qfine, &c->qfine_bytes, "query"},
-                     {rfine, c->r_off.back(), &c->rfine, &c->has_rfine, &c->rfine_bytes, "reference"}};
-    for (Side& s : sides) {
-        if (!s.x) continue;
-        *s.has = false;  // (until the new rows are down; for good if an element is refused: no half-written side is read)
-        *s.bytes = 0;
-        const int64_t rows = s.frames * regions;
-        // +64 rows of slack, zeroed: the 64-row tiles of the last video's last frames read past its end (fine_sim.hip)
-        const int64_t rows_out = round_up64(rows + 64, ROW_PAD);
-        VSC_TRY(s.buf->reserve((size_t)rows_out * c->fine_dpad * 2));
+    const int dpad = round_up(fdim, K_PAD);  // (halves per row: a multiple of 128 bytes, every 16-byte piece aligned)
+    return tn_set_fine(c, VSC_FINE_F16, regions, fdim, dpad * 2, qfine, rfine, [&](int side, const void* x, int64_t rows, void* dst, int64_t rows_out) {
         bool refused = false;
-        VSC_TRY(tn_encode_rows(c, s.x, src_f16 != 0, rows, fdim, c->fine_dpad, mem, s.buf->as<_Float16>(), rows_out, &refused));
-        c->ws.qn.release();  // (scratch of the encoder)
+        VSC_TRY(tn_encode_rows(c, x, src_f16 != 0, rows, fdim, dpad, mem, static_cast<_Float16*>(dst), rows_out, &refused));
         if (refused) {
+            const char* name = side ? "reference" : "query";
             set_error("vsc_tn_set_fine_f16: a %s fine descriptor holds NaN, +-inf or a value beyond +-65504, which a half float "
-                      "cannot store (the context keeps no %s fine descriptors)", s.name, s.name);
+                      "cannot store (the context keeps no %s fine descriptors)", name, name);
             return VSC_ERR_INVALID;
         }
-        *s.bytes = rows_out * c->fine_dpad * 2;
-        *s.has = true;
-    }
-    VSC_HIP(hipStreamSynchronize(c->stream));
-    return VSC_OK;
+        return VSC_OK;
+    });
 }
 
-int64_t vsc_tn_fine_bytes(const vsc_tn_ctx_t* c) { return c ? c->qfine_bytes + c->rfine_bytes : 0; }
+int64_t vsc_tn_fine_bytes(const vsc_tn_ctx_t* c) { return c ? c->fine.side[0].bytes + c->fine.side[1].bytes : 0; }
 
 int vsc_tn_fine_similarity(vsc_tn_ctx_t* c, const int32_t* pair_q, const int32_t* pair_r, int64_t n_pairs, int pairs_mem,
                            int symmetric, float* out, const int64_t* out_off, int64_t cap, int out_mem) {
@@ -1052,8 +944,9 @@ int vsc_tn_fine_similarity(vsc_tn_ctx_t* c, const int32_t* pair_q, const int32_t
     }
     if (n_pairs == 0) return VSC_OK;
     // (a side without frames needs no descriptors: no pair has a cell to fill)
-    if ((!c->has_qfine && c->q_off.back() > 0) || (!c->has_rfine && c->r_off.back() > 0)) {
-        set_error("vsc_tn_fine_similarity: the context has no %s fine descriptors (vsc_tn_set_fine)", c->has_qfine ? "reference" : "query");
+    const FineStore& f = c->fine;
+    if ((!f.side[0].has && c->q_off.back() > 0) || (!f.side[1].has && c->r_off.back() > 0)) {
+        set_error("vsc_tn_fine_similarity: the context has no %s fine descriptors (vsc_tn_set_fine)", f.side[0].has ? "reference" : "query");
         return VSC_ERR_INVALID;
     }
     VSC_HIP(hipSetDevice(c->device));
@@ -1066,7 +959,7 @@ int vsc_tn_fine_similarity(vsc_tn_ctx_t* c, const int32_t* pair_q, const int32_t
         VSC_HIP(hipStreamSynchronize(c->stream));
     }
     // capacity first: nothing is written when one pair does not fit
-    const int frames = fine_sim_frames(c->fine_regions);
+    const int frames = fine_sim_frames(f.regions);
     int64_t total = 0, n_work = 0;
     for (int64_t p = 0; p < n_pairs; ++p) {
         const int64_t lq = lqs[(size_t)p], lr = lrs[(size_t)p], cells = lq * lr;
@@ -1126,30 +1019,32 @@ int vsc_tn_fine_similarity(vsc_tn_ctx_t* c, const int32_t* pair_q, const int32_t
         a.pair_r = c->d_pr.as<int32_t>();
         a.work = c->d_fwork.as<int32_t>();
         a.n_work = (int)n_work;
-        a.regions = c->fine_regions;
-        a.fdim = c->fine_dim;
+        a.regions = f.regions;
+        a.fdim = f.dim;
         a.symmetric = symmetric != 0;
         a.err = c->d_ferr.as<int>();
         a.out = d_out;
         a.out_off = d_off;
     };
-    if (c->fine_kind == VSC_FINE_BITS) {
+    const DevBuf &qrows = f.side[0].rows, &rrows = f.side[1].rows;
+    if (f.kind == VSC_FINE_BITS) {
         FineBitsArgs a;
         bind(a);
-        a.qbits = c->qfine.as<uint4>();
-        a.rbits = c->rfine.as<uint4>();
-        a.w16 = c->fine_w16;
+        a.qbits = qrows.as<uint4>();
+        a.rbits = rrows.as<uint4>();
+        a.w16 = f.row_bytes / 16;
         VSC_TRY(launch_fine_bits(a, c->stream));
     } else {
+        const bool half_rows = f.kind == VSC_FINE_F16;
         FineSimArgs a;
         bind(a);
-        a.qfine = c->qfine.as<float>();
-        a.rfine = c->rfine.as<float>();
-        a.qfine_h = c->qfine.as<_Float16>();  // (the same buffers: the store's kind says which of the two is read)
-        a.rfine_h = c->rfine.as<_Float16>();
-        a.dpad = c->fine_dpad;
-        a.bin = c->fine_kind == VSC_FINE_BIN;
-        VSC_TRY(launch_fine_sim(a, c->stream, c->fine_kind == VSC_FINE_F16));
+        a.qfine = qrows.as<float>();
+        a.rfine = rrows.as<float>();
+        a.qfine_h = qrows.as<_Float16>();  // (the same buffers: the store's kind says which of the two is read)
+        a.rfine_h = rrows.as<_Float16>();
+        a.dpad = f.row_bytes / (half_rows ? 2 : 4);
+        a.bin = f.kind == VSC_FINE_BIN;
+        VSC_TRY(launch_fine_sim(a, c->stream, half_rows));
     }
     int err = 0;
     VSC_HIP(hipMemcpyAsync(&err, c->d_ferr.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
