@@ -17,7 +17,8 @@ Because `similarity()` is overridden, `localize_all` takes the reference's route
 `vsc2022_amd.vsc.baseline.localization.VCSLLocalization`: one matrix per pair (the coarse part computed on the
 GPU by libvscmi), alignment of all of them in one `vsc_tn_forward_sim` call, MaxSim score per box.
 
-`on_device=True` (opt-in; the default is the route above, unchanged) keeps every matrix in HBM.  Stage 1 produces the
+`on_device=True` (opt-in; the default is the route above, unchanged) keeps every matrix in HBM: `_device_route` then
+names `_launch_fine`, and the batch goes the base class's way from candidates to rows.  Stage 1 produces the
 fine matrices F = sim / 2 + 0.5 of a batch in one device slab: an exact `ChamferSimilarity` instance -- the part of a
 fine-grained student that has no weights -- runs in libvscmi on fine descriptors that went down once
 (`vsc_tn_set_fine`, `vsc_tn_fine_similarity`: region Chamfer on the matrix cores); any other model runs as before, per
@@ -211,17 +212,21 @@ class VCSLLocalizationDnS(VCSLLocalizationMaxSim):
 
     @torch.no_grad()
     def _model_fine(self, q: torch.Tensor, r: torch.Tensor) -> torch.Tensor:
-        """F of one pair by the torch model: the statements of `similarity`, on `torch_device`."""
+        """F of one pair by the torch model, on `torch_device`: for `similarity` and for the slab of the device route."""
         sim = self.sim_model(q, r)
         if self.symmetric:
             sim = (sim + self.sim_model(r, q).mT) / 2.0
         return sim / 2.0 + 0.5
 
+    def _load_fine(self, table, video_id) -> torch.Tensor:
+        """A video's fine descriptors as the model takes them: fp32 on `torch_device`, binaries rescaled."""
+        t = torch.from_numpy(np.asarray(table[video_id].feature)).to(self.torch_device).float()
+        return self._rescale_binaries(t)
+
     def _fine_tensor(self, table, video_id, cache) -> torch.Tensor:
         t = cache.get(video_id)
         if t is None:
-            t = torch.from_numpy(np.asarray(table[video_id].feature)).to(self.torch_device).float()
-            t = cache[video_id] = self._rescale_binaries(t)
+            t = cache[video_id] = self._load_fine(table, video_id)
         return t
 
     def _fine_slab(self, candidates, pair_q: np.ndarray, pair_r: np.ndarray):
@@ -251,42 +256,19 @@ class VCSLLocalizationDnS(VCSLLocalizationMaxSim):
         self._bind_stream()
         return slab, d_off
 
-    def _device_boxes(self, candidates):
-        """Both stages of a batch: the box table on the host, as `_fused_boxes` returns it."""
-        n = len(candidates)
-        pair_q, pair_r = self._pair_ordinals(candidates)
-        slab, d_off = self._fine_slab(candidates, pair_q, pair_r)
-        n_boxes = np.zeros(n, dtype=np.int32)
-        boxes = np.zeros((n, _lib.TN_MAX_BOXES, 4), dtype=np.int32)
-        box_max = np.zeros((n, _lib.TN_MAX_BOXES), dtype=np.float32)
+    def _device_route(self):
+        """on_device=True: both stages in HBM (`_launch_fine`).  Otherwise the base class's choice: with `similarity`
+        overridden here, the reference's route through it."""
+        return self._launch_fine if self.on_device else super()._device_route()
+
+    def _launch_fine(self, candidates, table):
+        """Both stages of a batch: the fine slab, then blend, alignment and scores (libvscmi vsc_tn_localize_fine)."""
+        slab, d_off = self._fine_slab(candidates, table.pair_q, table.pair_r)
         _lib.check(_lib.lib().vsc_tn_localize_fine(
-            self._ctx, pair_q.ctypes.data, pair_r.ctypes.data, n, _lib.MEM_HOST, slab.data_ptr(), d_off.data_ptr(),
-            _lib.MEM_DEVICE, int(bool(self.geometric_mean)), ctypes.byref(self.model.params), float(self.similarity_bias),
-            n_boxes.ctypes.data, boxes.ctypes.data, box_max.ctypes.data, _lib.MEM_HOST))
-        return pair_q, pair_r, n_boxes, boxes, box_max
-
-    def localize_all(self, candidates: List[CandidatePair]) -> List[Match]:
-        if not self.on_device:
-            return super().localize_all(candidates)
-        candidates = list(candidates)
-        if not candidates:
-            return []
-        _, _, n_boxes, boxes, box_max = self._device_boxes(candidates)
-        matches: List[Match] = []
-        for k, candidate in enumerate(candidates):
-            for b in range(int(n_boxes[k])):
-                match = self._to_match(candidate, [int(v) for v in boxes[k, b]])
-                matches.append(match._replace(score=self._fused_score(candidate, box_max[k, b])))
-        return matches
-
-    def localize_table(self, candidates: List[CandidatePair]):
-        if not self.on_device:
-            return super().localize_table(candidates)
-        candidates = candidates if hasattr(candidates, "columns") else list(candidates)
-        if len(candidates) == 0:
-            return M.MatchTable.empty()
-        pair_q, pair_r, n_boxes, boxes, box_max = self._device_boxes(candidates)
-        return self._device_rows(candidates, pair_q, pair_r, n_boxes, boxes, box_max)
+            self._ctx, table.pair_q.ctypes.data, table.pair_r.ctypes.data, len(table.pair_q), _lib.MEM_HOST, slab.data_ptr(),
+            d_off.data_ptr(), _lib.MEM_DEVICE, int(bool(self.geometric_mean)), ctypes.byref(self.model.params),
+            float(self.similarity_bias), table.n_boxes.ctypes.data, table.boxes.ctypes.data, table.box_max.ctypes.data,
+            _lib.MEM_HOST))
 
     def _device_similarity_fine(self, candidate: CandidatePair) -> np.ndarray:
         """S of one pair: stage 1 for it alone, blended by libvscmi (vsc_tn_similarity_fine)."""
@@ -307,13 +289,8 @@ class VCSLLocalizationDnS(VCSLLocalizationMaxSim):
     def similarity(self, candidate: CandidatePair):
         if self.on_device:
             return self._device_similarity_fine(candidate)
-        query = torch.from_numpy(np.asarray(self.queries_fine[candidate.query_id].feature)).to(self.torch_device).float()
-        ref = torch.from_numpy(np.asarray(self.refs_fine[candidate.ref_id].feature)).to(self.torch_device).float()
-        query, ref = self._rescale_binaries(query), self._rescale_binaries(ref)
-        sim = self.sim_model(query, ref)
-        if self.symmetric:
-            sim = (sim + self.sim_model(ref, query).mT) / 2.0
-        sim = (sim / 2.0 + 0.5).cpu().numpy()
+        sim = self._model_fine(self._load_fine(self.queries_fine, candidate.query_id),
+                               self._load_fine(self.refs_fine, candidate.ref_id)).cpu().numpy()
         if self.geometric_mean:
             coarse = self._device_similarity(candidate, self.similarity_bias)  # q @ r.T + bias, on the GPU
             sim = np.sqrt(sim.clip(1e-7) * coarse.clip(1e-7))

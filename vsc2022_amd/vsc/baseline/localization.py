@@ -6,20 +6,22 @@ Class surface of the reference module (`Localization`, `LocalizationWithMetadata
 /root/reference/vsc/baseline/localization.py:16-96).
 
 How it runs here: the constructor uploads both descriptor sets once into a libvscmi TN context
-(HBM resident).  `localize_all` then sends only the (query ordinal, reference ordinal) list of the
-batch; one workgroup per pair computes the frame x frame similarity on the matrix cores, runs the
-Temporal-Network alignment (or, with `on_device=True`, the DTW / DP one) and scores the boxes, and
-the host merely converts box corners to timestamps.  A subclass that overrides `score` (or
-`similarity`) in a way the fused kernel cannot know is still honoured: it falls back to the
-reference's route -- similarity matrices on the host, `self.model.forward_sim(...)`,
-`self.score(...)` per box.
+(HBM resident).  A batch then takes one route, the same for `localize_all` and `localize_table` (`_answer`):
+`_device_route` picks the launch function of the instance -- the fused Temporal-Network kernel, the DTW / DP one
+(`on_device=True`), a subclass's own -- or none; the candidate ids become ordinals once; the launch sends only that
+(query ordinal, reference ordinal) list and fills one `BoxTable` (one workgroup per pair computes the frame x frame
+similarity on the matrix cores, aligns and scores the boxes); the pairs the kernel did not finish (`status != 0`) --
+every pair, when a subclass overrides `score` or `similarity` in a way no kernel can know -- take the reference's
+route (`_reference_rows`: similarity matrices on the host, `self.model.forward_sim(...)`, `self.score(...)` per box)
+and are spliced back in candidate order.
 
-`localize_table` returns the rows of `localize_all` as a `vsc.metrics.MatchTable`: the timestamp tables are uploaded with
-the descriptors, and on the fused routes the box -> timestamp conversion is device work too (libvscmi vsc_tn_match_rows).
+The two methods differ in the last step only.  `localize_all` converts box corners to timestamps on the host, box by
+box (`box_matches`).  `localize_table` returns the same rows as a `vsc.metrics.MatchTable`: the timestamp tables are
+uploaded with the descriptors, and the box -> timestamp conversion is device work too (libvscmi vsc_tn_match_rows).
 """
 import abc
 import ctypes
-from typing import Dict, List, Sequence
+from typing import Dict, Iterable, Iterator, List, Mapping, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -60,6 +62,59 @@ def _time_dtype(videos: Sequence[VideoFeature], used: np.ndarray) -> np.dtype:
     pool = [videos[k] for k in used] if len(used) else list(videos)
     kinds = {np.asarray(v.timestamps).dtype for v in pool}
     return np.result_type(*kinds) if kinds else np.dtype(np.float64)
+
+
+class BoxTable(NamedTuple):
+    """The device's answer for a batch of n candidate pairs: host arrays, allocated here and filled by a launch function."""
+
+    pair_q: np.ndarray   # int32 [n]: the pairs' query video ordinals ...
+    pair_r: np.ndarray   # ... and reference video ordinals
+    n_boxes: np.ndarray  # int32 [n]
+    boxes: np.ndarray    # int32 [n, TN_MAX_BOXES, 4]: q_lo, r_lo, q_hi, r_hi (frame indices, inclusive ends)
+    box_max: np.ndarray  # fp32 [n, TN_MAX_BOXES]: the kernel's MaxSim score of every box
+    status: np.ndarray   # int32 [n]: != 0 where the kernel left the pair to the caller; all zero on routes that always finish
+
+    @classmethod
+    def zeros(cls, pair_q: np.ndarray, pair_r: np.ndarray) -> "BoxTable":
+        n = len(pair_q)
+        return cls(pair_q, pair_r, np.zeros(n, dtype=np.int32), np.zeros((n, _lib.TN_MAX_BOXES, 4), dtype=np.int32),
+                   np.zeros((n, _lib.TN_MAX_BOXES), dtype=np.float32), np.zeros(n, dtype=np.int32))
+
+    def unfinished(self) -> List[int]:
+        return np.flatnonzero(self.status).tolist()
+
+
+def box_matches(candidates: Sequence[CandidatePair], n_boxes, boxes, box_max, to_match, score,
+                spliced: Optional[Mapping[int, List[Match]]] = None) -> List[Match]:
+    """A box table as the matches of its batch, pair by pair in candidate order: `to_match(candidate, box)` with the
+    score `score(candidate, box_max[k, b])`.  spliced: {pair index: the matches another route found for that pair}; they
+    take the pair's place, whatever the table holds for it."""
+    spliced = spliced or {}
+    matches: List[Match] = []
+    for k, candidate in enumerate(candidates):
+        if k in spliced:
+            matches += spliced[k]
+            continue
+        for b in range(int(n_boxes[k])):
+            match = to_match(candidate, [int(v) for v in boxes[k, b]])
+            matches.append(match._replace(score=score(candidate, box_max[k, b])))
+    return matches
+
+
+def rows_table(rows: Iterable[Tuple[int, Match, Tuple[int, int, int, int]]]) -> MatchTable:
+    """`(pair index, match, box)` rows (`VCSLLocalization._reference_rows`) collected as columns."""
+    rows = list(rows)
+    return MatchTable.from_matches([match for _, match, _ in rows], pair=[k for k, _, _ in rows], boxes=[box for _, _, box in rows])
+
+
+def splice_rows(table: MatchTable, rows) -> MatchTable:
+    """The device's rows of a batch with the `(pair index, match, box)` rows of the pairs it did not finish (for which it
+    holds none) put in at their pairs' places: candidate order."""
+    rest = rows_table(rows)
+    if not len(rest):
+        return table
+    both = MatchTable.concat([table, rest])
+    return both.take(np.argsort(both.pair, kind="stable"))
 
 
 class LocalizationWithMetadata(Localization):
@@ -123,9 +178,7 @@ class LocalizationWithMetadata(Localization):
     def _device_similarity(self, candidate: CandidatePair, bias: float) -> np.ndarray:
         q, r = self._q_ordinal[candidate.query_id], self._r_ordinal[candidate.ref_id]
         out = np.empty((len(self._q_videos[q]), len(self._r_videos[r])), dtype=np.float32)
-        n_q, n_r = ctypes.c_int32(0), ctypes.c_int32(0)
-        _lib.check(_lib.lib().vsc_tn_similarity(self._ctx, q, r, float(bias), out.ctypes.data, out.size,
-                                                ctypes.byref(n_q), ctypes.byref(n_r)))
+        _lib.check(_lib.lib().vsc_tn_similarity(self._ctx, q, r, float(bias), out.ctypes.data, out.size, None, None))
         return out
 
     def similarity(self, candidate: CandidatePair):
@@ -148,25 +201,54 @@ class VCSLLocalization(LocalizationWithMetadata):
         """Similarity plus the optional bias (some aligners dislike negative values)."""
         return self._device_similarity(candidate, self.similarity_bias)
 
-    # -- the two ways of getting boxes ------------------------------------------------------
-    def _can_fuse(self) -> bool:
+    # -- which route, and the launch functions of the device routes ---------------------------------
+    def _device_route(self):
+        """The launch function of the device route this instance takes, `launch(candidates, table)` filling a zeroed
+        `BoxTable` -- `_launch_tn` for the TN model, `_launch_align` for an on-device DTW / DP model (`on_device=True`) --
+        or None for the reference's route: any other model, and a `score` or `similarity` that no kernel can know."""
+        from vsc2022_amd.vcsl import aligners
         from vsc2022_amd.vcsl.vta import TN
 
         stock_scores = (VCSLLocalization.score, VCSLLocalizationMaxSim.score, VCSLLocalizationCandidateScore.score)
-        return (type(self.model) is TN and type(self).score in stock_scores
-                and type(self).similarity is VCSLLocalization.similarity)
+        if type(self).score not in stock_scores or type(self).similarity is not VCSLLocalization.similarity:
+            return None
+        if type(self.model) is TN:
+            return self._launch_tn
+        if type(self.model) in (aligners.DTW, aligners.DP) and self.model.on_device:
+            return self._launch_align
+        return None
 
-    def _fused_boxes(self, candidates: Sequence[CandidatePair]):
+    def _can_fuse(self) -> bool:
+        return self._device_route() == self._launch_tn
+
+    def _can_fuse_align(self) -> bool:
+        return self._device_route() == self._launch_align
+
+    def _pair_ordinals(self, candidates):
         n = len(candidates)
-        pair_q = np.fromiter((self._q_ordinal[c.query_id] for c in candidates), dtype=np.int32, count=n)
-        pair_r = np.fromiter((self._r_ordinal[c.ref_id] for c in candidates), dtype=np.int32, count=n)
-        n_boxes = np.zeros(n, dtype=np.int32)
-        boxes = np.zeros((n, _lib.TN_MAX_BOXES, 4), dtype=np.int32)
-        box_max = np.zeros((n, _lib.TN_MAX_BOXES), dtype=np.float32)
+        return (np.fromiter((self._q_ordinal[c.query_id] for c in candidates), dtype=np.int32, count=n),
+                np.fromiter((self._r_ordinal[c.ref_id] for c in candidates), dtype=np.int32, count=n))
+
+    def _launch_tn(self, candidates, table: BoxTable):
+        """The fused Temporal-Network kernel (libvscmi vsc_tn_localize); finishes every pair."""
         _lib.check(_lib.lib().vsc_tn_localize(
-            self._ctx, pair_q.ctypes.data, pair_r.ctypes.data, n, _lib.MEM_HOST, ctypes.byref(self.model.params),
-            float(self.similarity_bias), n_boxes.ctypes.data, boxes.ctypes.data, box_max.ctypes.data, _lib.MEM_HOST))
-        return n_boxes, boxes, box_max
+            self._ctx, table.pair_q.ctypes.data, table.pair_r.ctypes.data, len(table.pair_q), _lib.MEM_HOST,
+            ctypes.byref(self.model.params), float(self.similarity_bias), table.n_boxes.ctypes.data, table.boxes.ctypes.data,
+            table.box_max.ctypes.data, _lib.MEM_HOST))
+
+    def _launch_align(self, candidates, table: BoxTable):
+        """The DTW / DP kernels (libvscmi vsc_tn_align); `status` names the pairs they hand back (too long for their LDS
+        state, too many boxes)."""
+        _lib.check(_lib.lib().vsc_tn_align(
+            self._ctx, table.pair_q.ctypes.data, table.pair_r.ctypes.data, len(table.pair_q), _lib.MEM_HOST,
+            ctypes.byref(self.model.params), float(self.similarity_bias), table.n_boxes.ctypes.data, table.boxes.ctypes.data,
+            table.box_max.ctypes.data, table.status.ctypes.data, _lib.MEM_HOST))
+
+    def _aligned_boxes(self, candidates: Sequence[CandidatePair]):
+        """`(n_boxes, boxes, box_max, status)` of one `_launch_align`."""
+        table = BoxTable.zeros(*self._pair_ordinals(candidates))
+        self._launch_align(candidates, table)
+        return table.n_boxes, table.boxes, table.box_max, table.status
 
     def _to_match(self, candidate: CandidatePair, box) -> Match:
         """Box corners are frame indices with inclusive ends: the segment runs from the start of the
@@ -177,85 +259,67 @@ class VCSLLocalization(LocalizationWithMetadata):
                      query_start=query.get_timestamps(x1)[0], query_end=query.get_timestamps(x2)[1],
                      ref_start=ref.get_timestamps(y1)[0], ref_end=ref.get_timestamps(y2)[1])
 
-    def _can_fuse_align(self) -> bool:
-        """An on-device DTW / DP model (`on_device=True`) with the stock `score` / `similarity`: the conditions of
-        `_can_fuse`, for the aligner kernels (libvscmi vsc_tn_align)."""
-        from vsc2022_amd.vcsl import aligners
-
-        stock_scores = (VCSLLocalization.score, VCSLLocalizationMaxSim.score, VCSLLocalizationCandidateScore.score)
-        return (type(self.model) in (aligners.DTW, aligners.DP) and self.model.on_device
-                and type(self).score in stock_scores and type(self).similarity is VCSLLocalization.similarity)
-
-    def _aligned_boxes(self, candidates: Sequence[CandidatePair]):
-        n = len(candidates)
-        pair_q = np.fromiter((self._q_ordinal[c.query_id] for c in candidates), dtype=np.int32, count=n)
-        pair_r = np.fromiter((self._r_ordinal[c.ref_id] for c in candidates), dtype=np.int32, count=n)
-        n_boxes = np.zeros(n, dtype=np.int32)
-        boxes = np.zeros((n, _lib.TN_MAX_BOXES, 4), dtype=np.int32)
-        box_max = np.zeros((n, _lib.TN_MAX_BOXES), dtype=np.float32)
-        status = np.zeros(n, dtype=np.int32)
-        _lib.check(_lib.lib().vsc_tn_align(
-            self._ctx, pair_q.ctypes.data, pair_r.ctypes.data, n, _lib.MEM_HOST, ctypes.byref(self.model.params),
-            float(self.similarity_bias), n_boxes.ctypes.data, boxes.ctypes.data, box_max.ctypes.data, status.ctypes.data,
-            _lib.MEM_HOST))
-        return n_boxes, boxes, box_max, status
-
-    def _reference_route(self, candidates: Sequence[CandidatePair]) -> List[List[Match]]:
-        """The reference's route: matrices on the host, any model, any score hook.  One list of matches per candidate."""
+    def _reference_rows(self, candidates: Sequence[CandidatePair], pair_index: Sequence[int]) -> Iterator[Tuple[int, Match, tuple]]:
+        """The reference's route: matrices on the host, any model, any score hook.  Yields `(pair index, match, box)` in
+        candidate order (pair_index: the candidates' positions in the batch).  A generator: no matrix is asked for before
+        the first row is, and none at all for no candidates."""
         named = [(f"{c.query_id}-{c.ref_id}", self.similarity(c)) for c in candidates]
+        if not named:
+            return
         results = self.model.forward_sim(named)
-        assert len(results) == len(candidates)
-        out: List[List[Match]] = []
-        for candidate, (key, sim), (name, pair_boxes) in zip(candidates, named, results):
+        assert len(results) == len(named)
+        for k, candidate, (key, sim), (name, pair_boxes) in zip(pair_index, candidates, named, results):
             assert key == name
-            matches = []
             for box in pair_boxes:
                 box = tuple(int(v) for v in box)
                 match = self._to_match(candidate, box)
-                matches.append(match._replace(score=self.score(candidate, match, box, sim)))
-            out.append(matches)
-        return out
+                yield k, match._replace(score=self.score(candidate, match, box, sim)), box
+
+    def _answer(self, candidates):
+        """The one route of a non-empty batch: `(table, rest)`.  table: the `BoxTable` the device route filled, None
+        without one; rest: the reference route's rows (`_reference_rows`, not started) of the pairs the device did not
+        finish -- of all pairs without a device route."""
+        launch = self._device_route()
+        if launch is None:
+            return None, self._reference_rows(candidates, range(len(candidates)))
+        table = BoxTable.zeros(*self._pair_ordinals(candidates))
+        launch(candidates, table)
+        left = table.unfinished()
+        return table, self._reference_rows([candidates[k] for k in left], left)
 
     def localize_all(self, candidates: List[CandidatePair]) -> List[Match]:
         candidates = list(candidates)
         if not candidates:
             return []
-        matches: List[Match] = []
-        if self._can_fuse():
-            n_boxes, boxes, box_max = self._fused_boxes(candidates)
-            for k, candidate in enumerate(candidates):
-                for b in range(int(n_boxes[k])):
-                    match = self._to_match(candidate, [int(v) for v in boxes[k, b]])
-                    matches.append(match._replace(score=self._fused_score(candidate, box_max[k, b])))
-            return matches
-        if self._can_fuse_align():
-            n_boxes, boxes, box_max, status = self._aligned_boxes(candidates)
-            # the pairs the kernel did not finish (too long for its LDS state, too many boxes) take the reference's
-            # route and are spliced back in candidate order
-            left = [k for k in range(len(candidates)) if status[k] != 0]
-            by_host = dict(zip(left, self._reference_route([candidates[k] for k in left]))) if left else {}
-            for k, candidate in enumerate(candidates):
-                if k in by_host:
-                    matches += by_host[k]
-                    continue
-                for b in range(int(n_boxes[k])):
-                    match = self._to_match(candidate, [int(v) for v in boxes[k, b]])
-                    matches.append(match._replace(score=self._fused_score(candidate, box_max[k, b])))
-            return matches
-        for pair_matches in self._reference_route(candidates):
-            matches += pair_matches
-        return matches
+        table, rest = self._answer(candidates)
+        if table is None:
+            return [match for _, match, _ in rest]
+        spliced = {k: [] for k in table.unfinished()}
+        for k, match, _ in rest:
+            spliced[k].append(match)
+        return box_matches(candidates, table.n_boxes, table.boxes, table.box_max, self._to_match, self._fused_score, spliced)
 
     def localize(self, candidate: CandidatePair) -> List[Match]:
         return self.localize_all([candidate])
 
-    # -- the same rows as columns ---------------------------------------------------------------
-    def _device_rows(self, candidates, pair_q, pair_r, n_boxes, boxes, box_max) -> MatchTable:
+    def localize_table(self, candidates: List[CandidatePair]) -> MatchTable:
+        """`localize_all(candidates)` as a MatchTable: the same rows in the same order, values and dtypes included
+        (`localize_table(c).to_matches() == localize_all(c)`, and `write_csv` writes the same file).  On the device
+        routes the timestamps are gathered on the device and there is no per-box Python."""
+        candidates = candidates if hasattr(candidates, "columns") else list(candidates)
+        if len(candidates) == 0:
+            return MatchTable.empty()
+        table, rest = self._answer(candidates)
+        if table is None:
+            return rows_table(rest)
+        return splice_rows(self._device_rows(candidates, table), rest)  # (the device's rows first, then the matrices of `rest`)
+
+    def _device_rows(self, candidates, table: BoxTable) -> MatchTable:
         """The box table of a batch -> its match rows, by the engine's match-rows stage (vsc_tn_match_rows: row offsets,
         timestamp gathers and the dense table are device work); ids and column dtypes are attached here."""
         if self._ts_error is not None:
             raise ValueError(f"localize_table needs numeric timestamps: {self._ts_error}")
-        n = len(candidates)
+        pair_q, pair_r, n_boxes, boxes, box_max, _ = table
         cap = int(n_boxes.sum(dtype=np.int64))
         pair = np.empty(cap, dtype=np.int32)
         corners = np.empty((cap, 4), dtype=np.int32)
@@ -263,8 +327,8 @@ class VCSLLocalization(LocalizationWithMetadata):
         times = np.empty((cap, 4), dtype=np.float64)
         n_rows = ctypes.c_int64(0)
         _lib.check(_lib.lib().vsc_tn_match_rows(
-            self._ctx, pair_q.ctypes.data, pair_r.ctypes.data, n, _lib.MEM_HOST, n_boxes.ctypes.data, boxes.ctypes.data,
-            box_max.ctypes.data, _lib.MEM_HOST, pair.ctypes.data, corners.ctypes.data, score.ctypes.data,
+            self._ctx, pair_q.ctypes.data, pair_r.ctypes.data, len(pair_q), _lib.MEM_HOST, n_boxes.ctypes.data,
+            boxes.ctypes.data, box_max.ctypes.data, _lib.MEM_HOST, pair.ctypes.data, corners.ctypes.data, score.ctypes.data,
             times.ctypes.data, cap, _lib.MEM_HOST, ctypes.byref(n_rows)))
         assert n_rows.value == cap
         q_ord, r_ord = pair_q[pair], pair_r[pair]
@@ -275,51 +339,6 @@ class VCSLLocalization(LocalizationWithMetadata):
         return MatchTable(q_ids[q_ord], r_ids[r_ord], self._fused_score_column(candidates, pair, score),
                           times[:, 0].astype(q_t), times[:, 1].astype(q_t), times[:, 2].astype(r_t),
                           times[:, 3].astype(r_t), pair.astype(np.int64), corners)
-
-    def _reference_table(self, candidates: Sequence[CandidatePair], pair_index: Sequence[int]) -> MatchTable:
-        """`_reference_route` with the rows collected as columns (pair_index: the candidates' positions in the batch)."""
-        named = [(f"{c.query_id}-{c.ref_id}", self.similarity(c)) for c in candidates]
-        results = self.model.forward_sim(named)
-        assert len(results) == len(candidates)
-        matches, pair, corners = [], [], []
-        for k, candidate, (key, sim), (name, pair_boxes) in zip(pair_index, candidates, named, results):
-            assert key == name
-            for box in pair_boxes:
-                box = tuple(int(v) for v in box)
-                match = self._to_match(candidate, box)
-                matches.append(match._replace(score=self.score(candidate, match, box, sim)))
-                pair.append(k)
-                corners.append(box)
-        return MatchTable.from_matches(matches, pair=pair, boxes=corners)
-
-    def localize_table(self, candidates: List[CandidatePair]) -> MatchTable:
-        """`localize_all(candidates)` as a MatchTable: the same rows in the same order, values and dtypes included
-        (`localize_table(c).to_matches() == localize_all(c)`, and `write_csv` writes the same file).  On the fused
-        routes the timestamps are gathered on the device and there is no per-box Python."""
-        candidates = candidates if hasattr(candidates, "columns") else list(candidates)
-        n = len(candidates)
-        if n == 0:
-            return MatchTable.empty()
-        if self._can_fuse():
-            n_boxes, boxes, box_max = self._fused_boxes(candidates)
-            pair_q, pair_r = self._pair_ordinals(candidates)
-            return self._device_rows(candidates, pair_q, pair_r, n_boxes, boxes, box_max)
-        if self._can_fuse_align():
-            n_boxes, boxes, box_max, status = self._aligned_boxes(candidates)
-            pair_q, pair_r = self._pair_ordinals(candidates)
-            table = self._device_rows(candidates, pair_q, pair_r, n_boxes, boxes, box_max)  # (nbox = 0 where status != 0)
-            left = [k for k in range(n) if status[k] != 0]
-            if not left:
-                return table
-            # the pairs the kernel did not finish take the reference's route and are spliced back in candidate order
-            both = MatchTable.concat([table, self._reference_table([candidates[k] for k in left], left)])
-            return both.take(np.argsort(both.pair, kind="stable"))
-        return self._reference_table(candidates, range(n))
-
-    def _pair_ordinals(self, candidates):
-        n = len(candidates)
-        return (np.fromiter((self._q_ordinal[c.query_id] for c in candidates), dtype=np.int32, count=n),
-                np.fromiter((self._r_ordinal[c.ref_id] for c in candidates), dtype=np.int32, count=n))
 
     def score(self, candidate: CandidatePair, match: Match, box, similarity) -> float:
         return 1.0
