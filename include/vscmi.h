@@ -741,6 +741,46 @@ int vsc_region_pool_l2_bf16(const void* x, float* out, int64_t B, int64_t H, int
  * row normaliser of the search API implements.  rows >= 0 (0: no-op), cols >= 1, eps >= 0. */
 int vsc_rows_l2norm_f32(float* x, int64_t rows, int64_t cols, float eps, void* hip_stream);
 
+/* ------------------------------------------------- frame transform of the inference CLI (--packed_batch)
+ * What the reference does to a decoded frame on the host (vsc/baseline/inference_impl.py:39-69: PIL image ->
+ * torchvision Resize / CenterCrop / ToTensor / Normalize), reproduced bit for bit for n uint8 RGB frames of DIFFERENT
+ * source sizes and one common output shape.  Per frame i: dense HWC source [src_h, src_w, 3] at src + src_off[i] ->
+ * resize to (dst_h, dst_w) -> window [top, top + out_h) x [left, left + out_w) -> value -> out.
+ *
+ * Resize = PIL's ImagingResample, 8-bit, BILINEAR (triangle filter, support 1), PRECISION_BITS = 22.  For one axis
+ * in -> out, every (int) truncating toward zero, all else in double:
+ *     scale = in / out;  fs = max(scale, 1.0);  support = fs;  ksize = (int)ceil(support) * 2 + 1
+ *     for xx in 0..out-1:
+ *         center = (xx + 0.5) * scale
+ *         xmin = max((int)(center - support + 0.5), 0)
+ *         xmax = min((int)(center + support + 0.5), in) - xmin                     (number of taps, <= ksize)
+ *         w[x] = max(0, 1 - |(x + xmin - center + 0.5) * (1.0 / fs)|)
+ *         ww = sum of w[x] in x order;  k[x] = w[x] / ww   (ww != 0)
+ *         K[x] = k < 0 ? (int)(-0.5 + k * 2^22) : (int)(0.5 + k * 2^22)            (int32)
+ *     out[xx] = clip8((sum_x in[xmin + x] * K[x] + 2^21) >> 22)      (int32 sum, arithmetic shift, clamp to 0..255)
+ * The horizontal pass runs first, the vertical pass second, and the image between them is uint8: rounded and clipped
+ * by the line above.  An axis with in == out is skipped: its data passes through untouched.  The int32 sum cannot
+ * overflow (255 * sum K ~ 2^30).
+ *
+ * Value: v = ((float)level / 255.0f - mean[c]) / std[c], three correctly rounded fp32 operations in that order
+ * (ToTensor, then Normalize with fp32 mean / std).  VSC_FRAME_OUT_F32_NCHW writes v to out [n, 3, out_h, out_w] float;
+ * VSC_FRAME_OUT_BF16_NHWC writes v rounded to nearest even to out [n, out_h, out_w, 3] bf16 (tensor.to(bfloat16)).
+ *
+ * The resize target and window of a transform (short edge to 288 / 320, centre crop with Python's half-to-even round)
+ * are the caller's: (dst_h, dst_w, top, left) are taken as given.  Only the rows and columns the window needs are
+ * computed.  The coefficient tables are built on the host, once per distinct (in, out) pair, and kept across calls.
+ * src and out are device pointers; every other array is host memory.  Limits, each VSC_ERR_INVALID with a message
+ * before any device call: 0 <= n <= 2^20 (0 is a no-op); 1 <= src_h, src_w <= 8192; 1 <= dst_h, dst_w <= 4096;
+ * out_h, out_w >= 1 and the window inside [0, dst) on both axes; src_off >= 0; std[c] != 0; a known out_format; no NULL
+ * pointer with n > 0.  Launches on `hip_stream` of the current device (NULL = the default stream), as the kernels
+ * above; calls on different streams share scratch memory and are ordered one after the other on the device. */
+#define VSC_FRAME_OUT_F32_NCHW 0  /* out [n, 3, oh, ow] float */
+#define VSC_FRAME_OUT_BF16_NHWC 1 /* out [n, oh, ow, 3] bf16 */
+int vsc_frame_transform_u8(const uint8_t* src, const int64_t* src_off, const int32_t* src_h, const int32_t* src_w,
+                           const int32_t* dst_h, const int32_t* dst_w, const int32_t* top, const int32_t* left, int64_t n,
+                           int out_h, int out_w, const float* mean, const float* std, int out_format, void* out,
+                           void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

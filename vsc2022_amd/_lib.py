@@ -48,6 +48,10 @@ FINE_BIN = 1
 FINE_BITS = 2  # the 1-bit store of BIN descriptors (vsc_tn_set_fine_bits): a context state, not a kind of vsc_tn_set_fine
 FINE_F16 = 3  # the half-float store of ATT descriptors (vsc_tn_set_fine_f16): a context state as well
 FINE_MAX_REGIONS = 16
+FRAME_OUT_F32_NCHW = 0  # VSC_FRAME_OUT_*: output layouts of vsc_frame_transform_u8
+FRAME_OUT_BF16_NHWC = 1
+FRAME_MAX_SRC = 8192  # limits of vsc_frame_transform_u8: source and resized edge lengths
+FRAME_MAX_DST = 4096
 ALIGN_MAX_CELLS = 9216  # VSC_ALIGN_MAX_CELLS: lq * lr of the largest pair whose working state fits LDS
 
 # every symbol include/vscmi.h declares
@@ -65,6 +69,7 @@ EXPORTS = (
     "vsc_aux_profile", "vsc_aux_profile_read", "vsc_bias_act_bf16", "vsc_gemm_bias_act_bf16", "vsc_pool3x3s2_bias_relu_bf16", "vsc_conv_bias_act_bf16",
     "vsc_vit_attention_bf16", "vsc_layernorm_bf16", "vsc_vit_tokens_bf16", "vsc_vit_cdpool_bf16",
     "vsc_region_pool_l2_bf16", "vsc_rows_l2norm_f32",
+    "vsc_frame_transform_u8",
 )
 
 
@@ -252,6 +257,7 @@ def lib():
         L.vsc_vit_cdpool_bf16.argtypes = [vp, vp, vp, vp, i64, i64, i64, f32, vp]
         L.vsc_region_pool_l2_bf16.argtypes = [vp, vp, i64, i64, i64, i64, i32, i32, i64, i64, f32, vp]
         L.vsc_rows_l2norm_f32.argtypes = [vp, i64, i64, f32, vp]
+        L.vsc_frame_transform_u8.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, i32, vp, vp]
         for name in EXPORTS:
             fn = getattr(L, name)
             if fn.restype is ctypes.c_int and name not in ("vsc_version", "vsc_device_count"):

@@ -13,6 +13,9 @@ inference.py:52-82) and mirrors its flow (`inference.py:93-158`, `inference_impl
     tensor ops instead of PIL + torchvision on the host);
   * batches of <= `--batch_size` frames of ONE video through the TorchScript model (`torch.jit.load`,
     `inference_impl.py:173`) -> one VideoFeature per video with `(i / fps, (i + 1) / fps)` timestamps;
+  * `--packed_batch N` (extension, `run_inference_packed`): frames of consecutive videos share batches of up to N frames,
+    and the transform is the reference's own arithmetic, bit for bit (`frame_transform`: PIL's integer bilinear resize,
+    crop, ToTensor, Normalize as one library call on the GPU); without it nothing changes;
   * `--store_fp16`; one `.npz` per rank under `--scratch_path`, merged into `--output_file` by
     `merge_feature_files` (`inference_impl.py:242-247`); `--processes N` spawns N workers on this machine
     (one per device with `--accelerator cuda`), `--distributed_rank/--distributed_size` for externally
@@ -199,6 +202,77 @@ def run_inference(dataset: Iterable, model, device, transform: InferenceTransfor
         yield VideoFeature(video_id=name, timestamps=ts, feature=np.concatenate(outs, axis=0))
 
 
+def _packed_output_format(model) -> str:
+    """bf16 NHWC once a `CheckedFast` has passed its gate and runs a `FastTrunk` (whose first step is that conversion);
+    fp32 NCHW otherwise -- the gate's batch included, which the fp32 eager network reads too."""
+    from vsc2022_amd.vsc.baseline.inference import FastTrunk
+
+    if isinstance(model, CheckedFast) and model.checked and model.use_fast and isinstance(model.fast, FastTrunk):
+        return "bf16"
+    return "f32"
+
+
+@torch.no_grad()
+def run_inference_packed(dataset: Iterable, model, device, transform: InferenceTransforms, packed_batch: int = 128,
+                         store_fp16: bool = False) -> Iterator[VideoFeature]:
+    """`run_inference` with frames of consecutive videos sharing batches of up to `packed_batch` frames (`--packed_batch`)
+    and the reference's preprocessing reproduced exactly (`frame_transform`: the library's kernels on a GPU, numpy on the
+    CPU).  Frames are bucketed by output shape (RESIZE_288 gives landscape and portrait shapes); a bucket is flushed
+    when it is full and at the end; one VideoFeature per video, in dataset order, with the dataset's timestamps.  In
+    eval mode a network treats every frame on its own, so the batch composition changes its efficiency only."""
+    from vsc2022_amd.vsc.baseline import frame_transform as ft
+
+    assert packed_batch > 0
+    device = torch.device(device)
+    buckets = {}   # (oh, ow) -> [(video record, first frame, uint8 frames [k, H, W, 3])]
+    videos = []    # in dataset order, not yet yielded: [name, timestamps, n_frames, {first frame: descriptors}]
+
+    def flush(key):
+        chunks = buckets.pop(key)
+        if device.type == "cuda":
+            # every chunk goes straight from its video's stack into one device buffer (no copy on the host); the
+            # library reads the chunks there in place
+            flat = torch.empty(sum(c.size for _, _, c in chunks), dtype=torch.uint8, device=device)
+            views, at = [], 0
+            for _, _, c in chunks:
+                views.append(flat[at : at + c.size].view(c.shape))
+                views[-1].copy_(torch.from_numpy(np.ascontiguousarray(c)))
+                at += c.size
+            x = ft.transform_device(views, transform, out=_packed_output_format(model))
+        else:
+            x = torch.from_numpy(np.concatenate([ft.transform_host(c, transform) for _, _, c in chunks]))
+        y = model(x).float().cpu()
+        y = y.half().numpy() if store_fp16 else y.numpy()
+        at = 0
+        for video, first, c in chunks:
+            video[3][first] = y[at : at + len(c)]
+            at += len(c)
+
+    def finished():
+        while videos and sum(len(d) for d in videos[0][3].values()) == videos[0][2]:
+            name, ts, _, parts = videos.pop(0)
+            yield VideoFeature(video_id=name, timestamps=ts, feature=np.concatenate([parts[k] for k in sorted(parts)], axis=0))
+
+    for name, ts, frames in dataset:
+        h, w = int(frames.shape[1]), int(frames.shape[2])
+        th, tw, _, _, oh, ow = ft.resize_plan(transform, h, w)
+        ft.check_limits(h, w, th, tw)
+        video = [name, ts, len(frames), {}]
+        videos.append(video)
+        at = 0
+        while at < len(frames):
+            bucket = buckets.setdefault((oh, ow), [])
+            take = min(len(frames) - at, packed_batch - sum(len(c) for _, _, c in bucket))
+            bucket.append((video, at, frames[at : at + take]))
+            at += take
+            if sum(len(c) for _, _, c in bucket) == packed_batch:
+                flush((oh, ow))
+                yield from finished()
+    for key in list(buckets):
+        flush(key)
+    yield from finished()
+
+
 def merge_feature_files(filenames: List[str], output_filename: str) -> int:
     features = []
     for fn in filenames:
@@ -304,8 +378,13 @@ def worker_process(args, rank: int, world_size: int, output_filename: str):
     dataset = VideoDataset(args.dataset_path, fps=args.fps, extensions=args.video_extensions.split(","),
                            distributed_rank=rank, distributed_world_size=world_size,
                            video_reader=VideoReaderType[args.video_reader.upper()], ffmpeg_path=args.ffmpeg_path)
-    vfs = list(run_inference(dataset, model, device, InferenceTransforms[args.transforms], args.batch_size,
-                             args.store_fp16))
+    packed_batch = getattr(args, "packed_batch", 0)
+    if packed_batch > 0:
+        vfs = list(run_inference_packed(dataset, model, device, InferenceTransforms[args.transforms], packed_batch,
+                                        args.store_fp16))
+    else:
+        vfs = list(run_inference(dataset, model, device, InferenceTransforms[args.transforms], args.batch_size,
+                                 args.store_fp16))
     store_features(output_filename, vfs)
     logger.info(f"Wrote worker {rank} features for {len(vfs)} videos to {output_filename}")
 
@@ -334,6 +413,10 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--fast_min_cosine", type=float, default=0.999,
                    help="(extension) --fast: the first batch is also run on the fp32 network; below this per-frame "
                         "cosine the run continues on the fp32 network")
+    g.add_argument("--packed_batch", type=int, default=0,
+                   help="(extension) N > 0: frames of consecutive videos share batches of up to N frames, and the frame "
+                        "transform is the reference's PIL resize reproduced exactly (the library's kernel with "
+                        "--accelerator cuda); 0: one batch never mixes videos, as in the reference")
     d = p.add_argument_group("Dataset")
     d.add_argument("--dataset_path", required=True)
     d.add_argument("--fps", default=1, type=float)
